@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the aom_dsp hot path on MI355X (contract: see the task prompt).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
+
+A plain run (no --full) sets the ring up, warms up, times the K steps and prints the ONE JSON line of the headline: metric, value, unit,
+n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.  --full adds everything else the default
+workload measures beside it: the oracle parity check, the per-kernel launch times, roofline, transport ceiling and counter traffic, the
+CPU baseline, the other sizes / precisions / workloads under "others", the strong-scaling search block at N > 1, and the full record
+(bench_full.json).  --dump-outputs DIR writes the last timed step's results of a SAD ring workload as DIR/<name>.npy (float32).
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU).  The frame is
 cut into N uniform tile columns (av1/common/tile_common.c:76-97); rank r owns column r and
@@ -37,7 +43,7 @@ from benchlib.dist import barrier, dist_setup  # noqa: E402
 from benchlib.encoder import run_cdef_search, run_compound_search, run_int_pro, run_tf, run_warp_error, run_wiener_stats  # noqa: E402
 from benchlib.filters import run_filters_ring  # noqa: E402
 from benchlib.inner_loop import run_inner_loop  # noqa: E402
-from benchlib.line import build_lines, emit_lines  # noqa: E402
+from benchlib.line import build_lines, emit_lines, headline_line  # noqa: E402
 from benchlib.sad import WORKLOADS, run_sad_diamond_lists, run_workload  # noqa: E402
 from benchlib.search import run_first_pass, run_launcher_dry_run, run_mesh, run_search, run_search_default  # noqa: E402
 from benchlib.txq import TXQ_WORKLOADS, run_txq  # noqa: E402
@@ -94,12 +100,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default=None,
-                    help="default: sad16x16_modeA_1080p_8bit (BASELINE.json's metric) at every N; with N > 1 the line also carries the "
+                    help="default: sad16x16_modeA_1080p_8bit (BASELINE.json's metric) at every N; with N > 1 and --full the line also carries the "
                          "strong-scaling search pipeline with its per-frame RCCL exchange as `strong_scaling_search`",
                     choices=sorted(WORKLOADS) + ["txq_1080p_8bit", "txq_4k_10bit", "search_4k_10bit", "inner_loop_4k_10bit", "default_search_4k_10bit", "cdef_search_4k_10bit",
                                                 "wiener_stats_4k", "warp_error_4k", "int_pro_4k_8bit", "tf_motion_search_4k_10bit", "sad_diamond_lists_4k_8bit", "first_pass_4k_10bit", "compound_search_4k_10bit",
                                                 "filters_ring_4k_10bit", "launcher_dry_run"] + sorted(VAR_WORKLOADS))
-    ap.add_argument("--others", default="auto", help="comma list of extra workloads reported under 'others' (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity check, per-kernel / roofline / ceiling figures, cpu baseline, the 'others' workloads, the "
+                         "strong-scaling block at N > 1 and the full record (a plain run times the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; SAD ring workloads)")
+    ap.add_argument("--others", default="auto", help="comma list of extra workloads reported under 'others' (N=1, --full only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--bit-depth", type=int, default=0, choices=[0, 8, 10],
                     help="audit aid: run the *_4k_10bit search / filter workloads on planes of this depth instead (0 = the workload's own); the line says so")
@@ -130,9 +141,11 @@ def main():
         run_launcher_dry_run(args, dist, rank, world)
         return
     default_multi = args.workload is None and dist is not None
+    if args.dump_outputs and args.workload is not None and args.workload not in WORKLOADS:
+        sys.exit("bench.py: --dump-outputs writes the SAD ring workloads' results; %s is not one" % args.workload)
     if args.workload is None:
         # ONE metric at every N: BASELINE.json's SAD-candidates/s on the 1080p 8-bit configuration, whole-job aggregate (tile columns are
-        # independent: weak scaling, no data-path collective).  With N > 1 the line additionally carries the strong-scaling search
+        # independent: weak scaling, no data-path collective).  With N > 1 and --full the line also carries the strong-scaling search
         # pipeline with its per-frame RCCL exchange as `strong_scaling_search`.
         args.workload = "sad16x16_modeA_1080p_8bit"
     dev = 0
@@ -145,8 +158,9 @@ def main():
     ctx = pkg.capi.Context(dev, None)
     orc = None
     try:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
-        import pyoracle as orc  # checker + cpu_baseline only
+        if args.full or args.workload not in WORKLOADS:   # (a plain run of a SAD ring checks nothing against it)
+            sys.path.insert(0, os.path.join(ROOT, "oracle"))
+            import pyoracle as orc  # checker + cpu_baseline only
     except Exception as e:  # pragma: no cover
         print("warning: oracle unavailable (%s): no parity spot check / cpu_baseline" % e, file=sys.stderr)
 
@@ -258,7 +272,14 @@ def main():
                           "roofline": r["roofline"], "cpu_baseline": r.get("cpu_baseline"), "per_size": r["per_size"]}))
         return
     main_res = run_workload(pkg, ctx, dist, dev, rank, world, args.workload, args.steps, args.warmup,
-                            not args.no_cpu_baseline and world == 1, orc)
+                            args.full and not args.no_cpu_baseline and world == 1, orc, full=args.full, dump_dir=args.dump_outputs)
+    if not args.full:
+        ctx.close()
+        if rank == 0:
+            print(json.dumps(headline_line(args, world, main_res), separators=(",", ":")), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     others, strong = [], None
     if world == 1:
         names = ([n for n in ("sad16x16_modeA_4k_8bit", "sad16x16_modeA_4k_10bit", "sad16x16_modeA_1080p_8bit_range32",

@@ -49,11 +49,34 @@ def _other_summary(o):
     return out
 
 
+def headline(args, world, main_res):
+    """The contract's keys of the SAD ring's line: all a plain run prints, and the head of the --full line."""
+    cfg = WORKLOADS[args.workload]
+    head = {
+        "metric": "SAD-candidates/s", "value": main_res["value"], "unit": "candidates/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "u8" if cfg["bit_depth"] == 8 else "u16", "data": "synthetic",
+        "config": {"workload": args.workload, "frame": "%dx%d" % (cfg["width"], cfg["height"]),
+                   "bit_depth": cfg["bit_depth"], "block": "16x16",
+                   "mode": "A: 1 sad16x16 @mv(0,0) + 1 sad16x16x4d (uniform in [-%d,%d]^2) per block" % (cfg.get("search_range", 64), cfg.get("search_range", 64)),
+                   "ring_frame_pairs_per_gpu": common.FRAMES_OVERRIDE or cfg["frames"], "candidates_per_step": main_res["candidates_per_step"],
+                   "partition": ("balanced tile columns (encoder.c:247-275)" if common.TILE_COLUMNS == "balanced" else "uniform tile columns (tile_common.c:76-97)") +
+                                ", one per GPU; no data-path collective",
+                   "clock_ramp_s": float(os.environ.get("AOMHIP_BENCH_RAMP_S", "0.25"))},
+    }
+    return head
+
+
+def headline_line(args, world, main_res):
+    """The plain run's line (floats to 5 significant digits, as in the --full line)."""
+    return _sig(headline(args, world, main_res))
+
+
 def build_lines(args, world, main_res, others, strong):
     """(full record, printed line).  The printed line carries the contract's keys, the roofline as flat scalars (the three north-star sizes
     side by side), the cpu baseline, the transform half of the metric and one summary scalar set per informational workload -- and stays
     under LINE_LIMIT bytes.  Everything else (per-size tables, stage timings, notes, cpu legs) is in the full record."""
-    cfg = WORKLOADS[args.workload]
     sad_all = [main_res] + [o for o in others if str(o.get("workload", "")).startswith("sad16x16_modeA")]
     roof_full = dict(main_res["roofline"])
     roof_full["sizes"] = {r_["workload"]: dict(r_["roofline"], candidates_per_s=r_["value"]) for r_ in sad_all}
@@ -71,19 +94,7 @@ def build_lines(args, world, main_res, others, strong):
     filt = next((o for o in others if o.get("workload") == "filters_ring_4k_10bit"), None)
     rest = [o for o in others if o not in txqs and o not in sad_all and o not in vars_ and o is not filt]
     cpu = main_res.get("cpu_baseline")
-    head = {
-        "metric": "SAD-candidates/s", "value": main_res["value"], "unit": "candidates/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"],
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "u8" if cfg["bit_depth"] == 8 else "u16", "data": "synthetic",
-        "config": {"workload": args.workload, "frame": "%dx%d" % (cfg["width"], cfg["height"]),
-                   "bit_depth": cfg["bit_depth"], "block": "16x16",
-                   "mode": "A: 1 sad16x16 @mv(0,0) + 1 sad16x16x4d (uniform in [-%d,%d]^2) per block" % (cfg.get("search_range", 64), cfg.get("search_range", 64)),
-                   "ring_frame_pairs_per_gpu": common.FRAMES_OVERRIDE or cfg["frames"], "candidates_per_step": main_res["candidates_per_step"],
-                   "partition": ("balanced tile columns (encoder.c:247-275)" if common.TILE_COLUMNS == "balanced" else "uniform tile columns (tile_common.c:76-97)") +
-                                ", one per GPU; no data-path collective",
-                   "clock_ramp_s": float(os.environ.get("AOMHIP_BENCH_RAMP_S", "0.25"))},
-    }
+    head = headline(args, world, main_res)
     full = dict(head, roofline=roof_full, cpu_baseline=cpu,
                 txq={t["workload"]: t for t in txqs} or None, strong_scaling_search=strong,
                 parity_frame0_and_last_slot=main_res["parity_frame0"], kernels=main_res["kernels"], others=others)

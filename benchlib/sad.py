@@ -200,18 +200,30 @@ class SadModeA:
                 c.free(d)
 
 
-def run_workload(pkg, ctx, dist, dev, rank, world, name, steps, warmup, want_cpu, orc):
+def run_workload(pkg, ctx, dist, dev, rank, world, name, steps, warmup, want_cpu, orc, full=True, dump_dir=None):
+    """The ring's headline (candidates/s over the timed steps); with `full` also the oracle parity check, the per-kernel launch times, the
+    roofline, the transport ceiling and the cpu baseline.  `dump_dir`: the last timed step's results are written there (dump_outputs)."""
     wl = SadModeA(pkg, ctx, name, rank, world, frames_per_rank=common.FRAMES_OVERRIDE or None)
-    wl.step()
-    ctx.sync()
-    ok = wl.check_frame0(orc) if orc is not None else None
+    ok = None
+    if full:
+        wl.step()
+        ctx.sync()
+        ok = wl.check_frame0(orc) if orc is not None else None
     wall, ev_ms = time_steps(wl, ctx, dist, dev, steps, warmup)
+    if dump_dir is not None:
+        dump_outputs(wl, dump_dir, rank, world)
     total = wl.cands_per_step
     if dist is not None:
         import torch
         t = torch.tensor([total], dtype=torch.float64, device=_red_device())
         dist.all_reduce(t)
         total = int(t.item())
+    if not full:
+        res = {"workload": name, "value": total * steps / wall, "unit": "candidates/s", "ms_per_step": wall / steps * 1e3,
+               "event_ms_per_step": ev_ms / steps, "candidates_per_step": total, "ring_frames": wl.ring,
+               "blocks_per_frame_this_rank": wl.blocks_per_frame, "tile_column_px": list(wl.tile)}
+        wl.free()
+        return res
     kx_ms = kernel_avg_ms(ctx, wl.launch_x4d, max(steps, 10))
     k1_ms = kernel_avg_ms(ctx, wl.launch_single, max(steps, 10))
     if wl.path == "sb":  # dominant (only) kernel of the step: all five candidates of every block in one launch
@@ -273,6 +285,27 @@ def run_workload(pkg, ctx, dist, dev, rank, world, name, steps, warmup, want_cpu
         res["cpu_baseline"] = wl.cpu_baseline(orc)
     wl.free()
     return res
+
+
+def dump_outputs(wl, out_dir, rank, world):
+    """What the last timed step handed back to its caller, as float32 (every SAD is below 2^24, so exactly): `sad_single` [ring, blocks] = the
+    mv (0,0) candidate of every block, `sad_x4d` [ring, blocks, 4] = its x4d group, both in raster block order (the bucketed path's
+    permutation undone), ring slot by ring slot.  Ranks > 0 of an N > 1 job write their own tile column's under a `_rank<r>` suffix."""
+    n, ring = wl.blocks_per_frame, wl.ring
+    c = wl.ctx
+    c.sync()
+    if wl.path == "sb":
+        got1, got4 = np.empty((ring, n), np.uint32), np.empty((ring, n, 4), np.uint32)
+        if n:
+            got1[:, wl.perm] = c.from_device(wl.d_sb_out1, (ring, n), np.uint32)
+            got4[:, wl.perm] = c.from_device(wl.d_sb_out4, (ring, n, 4), np.uint32)
+    else:
+        got1 = c.from_device(wl.d_out1, (ring, n), np.uint32) if n else np.empty((ring, 0), np.uint32)
+        got4 = c.from_device(wl.d_out4, (ring, n, 4), np.uint32) if n else np.empty((ring, 0, 4), np.uint32)
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "sad_single%s.npy" % sfx), got1.astype(np.float32))
+    np.save(os.path.join(out_dir, "sad_x4d%s.npy" % sfx), got4.astype(np.float32))
 
 
 def run_sad_diamond_lists(pkg, ctx, orc, steps, warmup, width=3840, height=2160, bd=8, frames=16):

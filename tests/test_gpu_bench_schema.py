@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("tile_columns", ["uniform", "balanced"])
 def test_forced_one_rank_run_emits_the_multi_gpu_schema(tile_columns):
     env = dict(os.environ, AOMHIP_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", AOMHIP_BENCH_RAMP_S="0.02")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--frames-per-gpu", "8",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--frames-per-gpu", "8",
                         "--tile-columns", tile_columns], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -46,11 +46,11 @@ def test_forced_one_rank_run_emits_the_multi_gpu_schema(tile_columns):
 
 
 def test_default_single_gpu_line_is_small_enough_for_the_driver_record(tmp_path):
-    """The driver keeps an 8 KB tail of the output: round 4's 31 KB default line was not parsed.  The default N = 1 run must end in ONE JSON
-    line under 8000 bytes that still carries the headline, the roofline (flat scalars) and the cpu baseline; everything else is in the side file."""
+    """The driver keeps an 8 KB tail of the output: round 4's 31 KB default line was not parsed.  The default N = 1 --full run must end in ONE
+    JSON line under 8000 bytes that still carries the headline, the roofline (flat scalars) and the cpu baseline; everything else is in the side file."""
     full = tmp_path / "bench_full.json"
     env = dict(os.environ, AOMHIP_BENCH_RAMP_S="0.02", AOMHIP_BENCH_FULL=str(full), AOMHIP_BENCH_CPU_SECONDS="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], env=env, cwd=ROOT, capture_output=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-2000:]
     out_lines = p.stdout.splitlines()

@@ -1,50 +1,46 @@
 """Deblocking oracle:
   * the box-filter formulation of filter6/8/14 == the reference's literal tap listings, by evaluating the
     reference's own `*opN = ROUND_POWER_OF_TWO(<expr>, s);` statements (aom_dsp/loopfilter.c) on random
-    pixels (live when /root/reference exists);
+    pixels (recorded in tests/golden/ref_eval_lpf_flat.npz);
   * known behaviour: a flat region passes unchanged; level 0 / len 0 leave the plane untouched;
   * the whole-plane driver in the reference's superblock-row order == "all vertical then all horizontal"
     on random transform partitions (the independence property of SURVEY 8(a'), kept as a permanent test);
   * edges of one pass are order-independent (left-to-right == right-to-left)."""
-import re
+import os
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, have_reference
+from conftest import ROOT
+
+GOLD = os.path.join(ROOT, "tests", "golden")
 
 
-def _ref_flat_exprs():
-    src = open(REFERENCE + "/aom_dsp/loopfilter.c").read()
-    out = {}
-    for name in ("filter6", "filter8", "filter14"):
-        m = re.search(r"static INLINE void %s\(.*?\n\}" % name, src, re.S)
-        body = m.group(0)
-        stm = re.findall(r"\*o([pq]\d) = ROUND_POWER_OF_TWO\((.*?),\s*(\d)\);", body, re.S)
-        out[name] = [(t, re.sub(r"\s+", " ", e), int(s)) for t, e, s in stm]
-    return out
+def _ref_flat_vectors():
+    """{name: (rows, want)}: the seeded flat rows (p6..p0 q0..q6) and what the reference's own tap statements make of them
+    (tests/golden/gen_ref_eval_live.py, recorded from aom_dsp/loopfilter.c)."""
+    g = np.load(os.path.join(GOLD, "ref_eval_lpf_flat.npz"))
+    assert [int(g[n + "/statements"]) for n in ("filter6", "filter8", "filter14")] == [4, 6, 12]
+    return {n: (g[n + "/rows"], g[n + "/want"]) for n in ("filter6", "filter8", "filter14")}
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference")
 def test_flat_filters_equal_reference_tap_listings(oracle):
-    exprs = _ref_flat_exprs()
-    assert [len(v) for v in exprs.values()] == [4, 6, 12]
+    vecs = _ref_flat_vectors()
     rng = np.random.default_rng(1)
     for name, length in (("filter6", 6), ("filter8", 8), ("filter14", 14)):
-        for _ in range(200):
+        rows, wants = vecs[name]
+        assert len(rows) == 200
+        for row, exp in zip(rows.tolist(), wants.tolist()):
+            # the recorded rows are this rng's stream: the inputs are the ones the statements were evaluated on
             base = int(rng.integers(2, 250))
             taps = {("p%d" % i): base + int(rng.integers(-1, 2)) for i in range(7)}
             taps.update({("q%d" % i): base + int(rng.integers(-1, 2)) for i in range(7)})
+            assert row == [taps["p%d" % i] for i in range(6, -1, -1)] + [taps["q%d" % i] for i in range(7)]
             # flat region (all within 1 of p0/q0) with generous limits -> the flat branch is taken
             px = np.zeros((4, 16), np.uint8)
-            row = [taps["p%d" % i] for i in range(6, -1, -1)] + [taps["q%d" % i] for i in range(7)]
             px[:, 1:15] = row
-            want = dict(taps)
-            for t, e, s in exprs[name]:
-                want[t] = (eval(e, {}, taps) + (1 << (s - 1))) >> s
             oracle.lpf_edge(px, 0, 8, True, length, 255, 255, 0)
             got = px[0, 1:15].tolist()
-            exp = [want["p%d" % i] for i in range(6, -1, -1)] + [want["q%d" % i] for i in range(7)]
             if abs(taps["p0"] - taps["q0"]) * 2 + abs(taps["p1"] - taps["q1"]) // 2 <= 255:
                 flat_ok = all(abs(taps["p%d" % i] - taps["p0"]) <= 1 and abs(taps["q%d" % i] - taps["q0"]) <= 1
                               for i in range(1, {6: 3, 8: 4, 14: 7}[length]))

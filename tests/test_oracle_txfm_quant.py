@@ -1,8 +1,8 @@
 """Pins the oracle's transforms, tables and scans:
   * every 1-D butterfly network == the committed golden vectors that were produced by evaluating
-    the reference's own statements (tests/golden/make_golden.py), and == a live re-evaluation when
-    /root/reference is present;
-  * every constant table == the reference initialiser (live) / its committed sha256;
+    the reference's own statements (tests/golden/make_golden.py), and == a second recorded evaluation on other
+    seeded inputs (tests/golden/ref_eval_txfm1d_live.npz);
+  * every constant table == the reference initialiser (recorded) / its committed sha256;
   * forward 2-D transform within the reference gtest's double-precision error bounds
     (test/av1_fwd_txfm2d_test.cc:145-187), inverse(forward(x)) within test/av1_inv_txfm2d_test.cc's;
   * quantize_b: definitional properties here; pinned against the interpreted reference in test_golden_ref_eval.py."""
@@ -10,12 +10,11 @@ import hashlib
 import json
 import math
 import os
-import sys
 
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, have_reference
+from conftest import ROOT
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -45,18 +44,19 @@ def test_txfm1d_networks_match_reference_goldens(oracle):
                 assert np.array_equal(got, want[row]), (name, cb, clamp, row)
 
 
-@pytest.mark.skipif(not have_reference(), reason="live re-evaluation needs /root/reference")
 def test_txfm1d_networks_live_reference(oracle):
-    sys.path.insert(0, GOLD)
-    import ref_txfm1d_eval as rt
-    fns, cospi, _ = rt.load_reference_networks()
-    rng = np.random.default_rng(7)
-    for name, fn in fns.items():
-        inv, kind, size = name.startswith("av1_i"), (1 if "adst" in name else 0), fn[0]
-        x = rng.integers(-(1 << 17), 1 << 17, size=(20, size), dtype=np.int64)
+    """every network on seeded inputs: the reference's own statements evaluated by tests/golden/ref_txfm1d_eval.py, recorded in
+    tests/golden/ref_eval_txfm1d_live.npz (tests/golden/gen_ref_eval_live.py)"""
+    g = np.load(os.path.join(GOLD, "ref_eval_txfm1d_live.npz"))
+    names = sorted({k.split("/")[0] for k in g.files})
+    assert len(names) == 14
+    for name in names:
+        x = g[name + "/in"]
+        inv, kind = name.startswith("av1_i"), (1 if "adst" in name else 0)
+        assert x.shape[0] == 20
         for cb in (10, 13) if not inv else (12,):
             clamp = 18 if inv else 0
-            want = rt.evaluate(fn, x, cb, cospi[cb - 10], clamp)
+            want = g["%s/cb%d/clamp%d" % (name, cb, clamp)]
             for r in range(20):
                 got = oracle.inv_txfm1d(kind, x[r], cb, clamp) if inv else oracle.fwd_txfm1d(kind, x[r], cb)
                 assert np.array_equal(got, want[r])
@@ -89,14 +89,12 @@ def test_scan_tables(oracle, sums):
             assert sorted(scan.tolist()) == list(range(scan.size))
 
 
-@pytest.mark.skipif(not have_reference(), reason="needs /root/reference")
 def test_tables_live_reference(oracle):
-    sys.path.insert(0, GOLD)
-    import ref_txfm1d_eval as rt
-    assert oracle.cospi_table().ravel().tolist() == rt.parse_int_table(REFERENCE + "/av1/common/av1_txfm.c", "av1_cospi_arr_data")
-    assert oracle.sinpi_table().ravel().tolist() == rt.parse_int_table(REFERENCE + "/av1/common/av1_txfm.c", "av1_sinpi_arr_data")
-    want = rt.parse_int_table(REFERENCE + "/av1/common/scan.c", "default_scan_16x16")
-    assert oracle.get_scan(2, 0)[0].tolist() == want
+    """the reference's initialisers themselves (av1_txfm.c, scan.c), recorded in tests/golden/ref_eval_live_tables.json"""
+    t = json.load(open(os.path.join(GOLD, "ref_eval_live_tables.json")))
+    assert oracle.cospi_table().ravel().tolist() == t["av1_cospi_arr_data"]
+    assert oracle.sinpi_table().ravel().tolist() == t["av1_sinpi_arr_data"]
+    assert oracle.get_scan(2, 0)[0].tolist() == t["default_scan_16x16"]
 
 
 # ---------------------------------------------------------------- 2-D forward: reference gtest tolerance

@@ -1,18 +1,15 @@
 """Mechanical boundary check: every exact-signature entry point of include/aomhip.h whose name exists in the reference's
 rtcd definition files must have the reference's return type and parameter types, compared token by token after the preprocessor has
-expanded the header's stamping macros.  The prototypes are read from the `add_proto` lines of aom_dsp/aom_dsp_rtcd_defs.pl and
-av1/common/av1_rtcd_defs.pl where they lie under /root/reference (skipped where the reference is absent, e.g. on the GPU box)."""
+expanded the header's stamping macros.  The prototypes are those of the `add_proto` lines of aom_dsp/aom_dsp_rtcd_defs.pl and
+av1/common/av1_rtcd_defs.pl, normalised by _signature below and recorded in tests/golden/ref_eval_rtcd_protos.json
+(tests/golden/gen_ref_eval_live.py)."""
+import json
 import os
 import re
 import subprocess
 
-import pytest
+from conftest import ROOT
 
-from conftest import BLOCK_SIZES, REFERENCE, ROOT, have_reference
-
-pytestmark = pytest.mark.skipif(not have_reference(), reason="needs /root/reference")
-
-PL_FILES = ["aom_dsp/aom_dsp_rtcd_defs.pl", "av1/common/av1_rtcd_defs.pl"]
 TYPE_WORDS = {"int", "char", "short", "long", "unsigned", "signed", "void", "float", "double", "const", "struct"}
 # the reference's typedefs -> the C types the header spells out
 ALIASES = {"tran_low_t": "int32_t", "uint32_t": "unsigned int", "unsigned": "unsigned int", "TX_TYPE": "int", "TxfmParam": "void",
@@ -52,20 +49,9 @@ def _signature(ret, args):
 
 
 def reference_protos():
-    protos = {}
-    for rel in PL_FILES:
-        text = open(os.path.join(REFERENCE, rel)).read()
-        for m in re.finditer(r'add_proto\s+qw/([^/]*)/\s*,\s*(?:"([^"]+)"\s*,\s*)?"([^"]*)"\s*;', text):
-            head, name, args = m.group(1).split(), m.group(2), m.group(3)
-            if name is None:
-                name, head = head[-1], head[:-1]
-            ret = " ".join(head)
-            names = [name]
-            if "${w}" in name or "${h}" in name:
-                names = [name.replace("${w}", str(w)).replace("${h}", str(h)) for w, h in BLOCK_SIZES]
-            for n in names:
-                protos[n] = _signature(ret, args)  # (a name declared twice: the later add_proto wins, build/cmake/rtcd.pl add_proto)
-    return protos
+    """{name: (return type, [parameter types])} of every add_proto, the ${w} / ${h} stamped names expanded over the 22 block sizes."""
+    with open(os.path.join(ROOT, "tests", "golden", "ref_eval_rtcd_protos.json")) as f:
+        return {n: (r, list(p)) for n, (r, p) in json.load(f).items()}
 
 
 def header_protos():

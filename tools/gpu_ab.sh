@@ -6,7 +6,7 @@ python -m pytest tests -x -q -m gpu 2>&1 | tail -3
 for round in 1 2; do
 for v in $VALS; do
   echo "== $VAR=$v round $round"
-  env $VAR=$v python bench.py --steps 20 --warmup 3 --workload $WL --others "" --no-cpu-baseline | python -c "
+  env $VAR=$v python bench.py --full --steps 20 --warmup 3 --workload $WL --others "" --no-cpu-baseline | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('value %.4g cand/s  ms/step %.4f  x4d_ms %.4f cand_ms %.4f parity %s' % (d['value'], d['ms_per_step'], d['kernels']['sad_x4d_kernel_avg_ms'], d['kernels']['sad_cand_kernel_avg_ms'], d['parity_frame0']))"
 done

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 for C in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum"; do
   N=$(echo $C | tr ' ' '_')
   timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/$N -o pmc -- \
-      python bench.py --steps 5 --warmup 1 --workload $WL --others "" --no-cpu-baseline > $OUT/$N.json 2> $OUT/$N.err
+      python bench.py --full --steps 5 --warmup 1 --workload $WL --others "" --no-cpu-baseline > $OUT/$N.json 2> $OUT/$N.err
   ls $OUT/$N | head -5
 done
 f=$(find $OUT/FETCH_SIZE -name '*counter_collection.csv' | head -1); [ -n "$f" ] && head -5 "$f"

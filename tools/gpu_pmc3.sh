@@ -10,7 +10,7 @@ while read -r C; do
   [ -z "$C" ] && continue
   i=$((i+1))
   timeout 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/g$i -o pmc -- \
-      python bench.py --steps 3 --warmup 1 --workload $WL --others "" --no-cpu-baseline > $OUT/g$i.json 2> $OUT/g$i.err
+      python bench.py --full --steps 3 --warmup 1 --workload $WL --others "" --no-cpu-baseline > $OUT/g$i.json 2> $OUT/g$i.err
   tail -2 $OUT/g$i.err
 done <<'LIST'
 FETCH_SIZE
