@@ -226,6 +226,8 @@ _protos = {
     "aomhip_warp_error_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp]),
     "aomhip_segmented_frame_error": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _i, _vp]),
     "aomhip_quantize_lp_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "aomhip_block_error_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "aomhip_block_error_lp_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
     "aomhip_xform_quant_qm_batch": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aomhip_subtract_xform_quant_qm_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aomhip_encode_inter_blocks_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
@@ -340,6 +342,18 @@ for _name in RTCD_STAMPED + ["aomhip_fwd_txfm2d", "aomhip_inv_txfm2d_add", "aomh
 for _name, _res in (("aomhip_lf_build_edge_params", C.c_int), ("aomhip_lf_level_table", None), ("aomhip_cdef_build_skip8x8", C.c_int),
                     ("aomhip_cdef_build_strengths", C.c_int), ("aomhip_cdef_find_dir", C.c_int), ("aomhip_rtcd", C.c_int), ("aomhip_status", C.c_int), ("aomhip_failure_count", C.c_long)):
     getattr(lib, _name).restype = _res
+    _protos[_name] = (_res, None)
+
+# The av1_rtcd transform / quantisation surface (aomhip_rtcd_av1's table): its macro-stamped names, kept apart from RTCD_STAMPED, and the rest.
+RTCD_AV1_STAMPED = (["aomhip_highbd_inv_txfm_add_%dx%d" % wh for wh in RTCD_TX_SIZES] +
+                    ["aomhip_quantize_fp%s" % sz for sz in ("", "_32x32", "_64x64")])
+for _name, _res in ([(n, None) for n in RTCD_AV1_STAMPED] +
+                    [(n, None) for n in ("aomhip_inv_txfm_add", "aomhip_highbd_inv_txfm_add", "aomhip_highbd_iwht4x4_1_add", "aomhip_highbd_iwht4x4_16_add",
+                                         "aomhip_lowbd_fwd_txfm", "aomhip_fwht4x4", "aomhip_round_shift_array", "aomhip_highbd_quantize_fp",
+                                         "aomhip_quantize_lp", "aomhip_cdef_copy_rect8_8bit_to_16bit", "aomhip_cdef_copy_rect8_16bit_to_16bit")] +
+                    [("aomhip_block_error", C.c_int64), ("aomhip_block_error_lp", C.c_int64), ("aomhip_highbd_block_error", C.c_int64),
+                     ("aomhip_rtcd_av1", C.c_int)]):
+    getattr(lib, _name).restype = _res  # raises AttributeError if the library lacks the symbol
     _protos[_name] = (_res, None)
 
 EXPORTED = sorted(_protos)
@@ -653,6 +667,14 @@ class Context:
         """av1_quantize_lp on int16 coefficients (+ av1_block_error_lp into d_err): qparams carries round_fp / quant_fp in its round / quant fields"""
         check(lib.aomhip_quantize_lp_batch(self.h, d_coeff, tx_size, d_blocks, n_blocks, tx_type, C.byref(qparams), d_qcoeff, d_dqcoeff, d_eob, d_err),
               "aomhip_quantize_lp_batch")
+
+    def block_error_batch(self, d_coeff, d_dqcoeff, n_coeffs, n_blocks, is_hbd, bit_depth, d_out):
+        """av1_block_error / av1_highbd_block_error per block of n_coeffs int32 pairs -> d_out[2 i] = error, [2 i + 1] = ssz (int64)"""
+        check(lib.aomhip_block_error_batch(self.h, d_coeff, d_dqcoeff, n_coeffs, n_blocks, int(is_hbd), bit_depth, d_out), "aomhip_block_error_batch")
+
+    def block_error_lp_batch(self, d_coeff, d_dqcoeff, n_coeffs, n_blocks, d_out):
+        """av1_block_error_lp per block of n_coeffs int16 pairs -> one int64 per block"""
+        check(lib.aomhip_block_error_lp_batch(self.h, d_coeff, d_dqcoeff, n_coeffs, n_blocks, d_out), "aomhip_block_error_lp_batch")
 
     def xform_quant_qm_batch(self, d_residual, stride, tx_size, d_blocks, n_blocks, grid_cols, tx_type, qparams, is_hbd, d_qm, d_iqm, d_coeff, d_qcoeff,
                              d_dqcoeff, d_eob):

@@ -225,6 +225,50 @@ template <int LPB> __device__ __forceinline__ int group_max(int v) {
   return v;
 }
 
+template <int LPB> __device__ __forceinline__ int64_t group_sum64(int64_t v) {
+#pragma unroll
+  for (int m = 1; m < LPB; m <<= 1) v += __shfl_xor((long long)v, m, 64);
+  return v;
+}
+// one term pair of av1_block_error_c / av1_highbd_block_error_c (av1/encoder/rdopt.c:635-682): err_shift < 0 selects the
+// low-bd form, whose products are 32-bit (`diff * diff` on int operands wraps exactly as the compiled reference does)
+__device__ __forceinline__ void block_err_acc(int32_t c, int32_t dq, int err_shift, int64_t &e, int64_t &z) {
+  const int32_t diff = c - dq;
+  if (err_shift < 0) {
+    e += (int64_t)(int32_t)((uint32_t)diff * (uint32_t)diff);
+    z += (int64_t)(int32_t)((uint32_t)c * (uint32_t)c);
+  } else {
+    e += (int64_t)diff * diff;
+    z += (int64_t)c * c;
+  }
+}
+__device__ __forceinline__ void block_err_store(int64_t *out, int bi, int64_t e, int64_t z, int err_shift) {
+  if (err_shift > 0) {
+    const int64_t r = (int64_t)1 << (err_shift - 1);
+    e = (e + r) >> err_shift;
+    z = (z + r) >> err_shift;
+  }
+  out[2 * (int64_t)bi] = e;
+  out[2 * (int64_t)bi + 1] = z;
+}
+// av1_quantize_lp_c (av1/encoder/av1_quantize.c:212-240) for one int16 coefficient: |c| + round saturates at INT16_MAX, the level is
+// (that * quant) >> 16, and dqcoeff is the product's low 16 bits (the reference stores it through an int16_t).  Returns the level's
+// magnitude (the eob test).
+__device__ __forceinline__ int quantize_one_lp(int c, int round, int quant, int dequant, int16_t *qout, int16_t *dqout) {
+  const int sign = c >> 31;
+  int t = min((c ^ sign) - sign + round, 32767);
+  t = (t * quant) >> 16;
+  const int16_t qv = (int16_t)((t ^ sign) - sign);
+  *qout = qv;
+  *dqout = (int16_t)(qv * dequant);
+  return t;
+}
+// one term of av1_block_error_lp_c (av1/encoder/rdopt.c:650-660): the square in 32-bit wrap-around arithmetic like the compiled `int`
+__device__ __forceinline__ int64_t block_err_lp_term(int c, int dq) {
+  const uint32_t d = (uint32_t)(c - dq);
+  return (int32_t)(d * d);
+}
+
 
 // The lanes of a transform block (max(W, H) <= 64 adjacent lanes, a power of two) sit in ONE wavefront and a wavefront's LDS instructions
 // execute in program order: what one lane wrote is there for the block's other lanes as soon as the compiler keeps the accesses in order --

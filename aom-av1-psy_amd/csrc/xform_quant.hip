@@ -24,33 +24,6 @@
 #include "txb_cost_table.inc"
 
 namespace aomhip {
-template <int LPB> __device__ __forceinline__ int64_t group_sum64(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < LPB; m <<= 1) v += __shfl_xor((long long)v, m, 64);
-  return v;
-}
-// one term pair of av1_block_error_c / av1_highbd_block_error_c (av1/encoder/rdopt.c:635-682): err_shift < 0 selects the
-// low-bd form, whose products are 32-bit (`diff * diff` on int operands wraps exactly as the compiled reference does)
-__device__ __forceinline__ void block_err_acc(int32_t c, int32_t dq, int err_shift, int64_t &e, int64_t &z) {
-  const int32_t diff = c - dq;
-  if (err_shift < 0) {
-    e += (int64_t)(int32_t)((uint32_t)diff * (uint32_t)diff);
-    z += (int64_t)(int32_t)((uint32_t)c * (uint32_t)c);
-  } else {
-    e += (int64_t)diff * diff;
-    z += (int64_t)c * c;
-  }
-}
-__device__ __forceinline__ void block_err_store(int64_t *out, int bi, int64_t e, int64_t z, int err_shift) {
-  if (err_shift > 0) {
-    const int64_t r = (int64_t)1 << (err_shift - 1);
-    e = (e + r) >> err_shift;
-    z = (z + r) >> err_shift;
-  }
-  out[2 * (int64_t)bi] = e;
-  out[2 * (int64_t)bi + 1] = z;
-}
-
 constexpr int kXqThreads = 256;
 
 struct __attribute__((packed, aligned(1))) VecU128 { uint32_t v[4]; };
@@ -737,16 +710,13 @@ __global__ __launch_bounds__(256) void quant_lp_kernel(const int16_t *__restrict
   int64_t e = 0;
   for (int rc = lane; rc < NC; rc += 64) {
     const int ac = rc != 0;
-    const int c = coeff[off + rc], sign = c >> 31;
-    int t = min((c ^ sign) - sign + (int)(int16_t)qa.round[ac], 32767);
-    t = (t * (int)(int16_t)qa.quant[ac]) >> 16;
-    const int16_t qv = (int16_t)((t ^ sign) - sign);
-    const int16_t dv = (int16_t)(qv * (int)(int16_t)qa.dequant[ac]);
+    const int c = coeff[off + rc];
+    int16_t qv, dv;
+    const int t = quantize_one_lp(c, qa.round[ac], qa.quant[ac], qa.dequant[ac], &qv, &dv);
     qcoeff[off + rc] = qv;
     dqcoeff[off + rc] = dv;
     if (t) last = max(last, iscan_pos<KW, KH>(rc % KH, rc / KH, scan_class) + 1);
-    const uint32_t d = (uint32_t)(c - dv);
-    e += (int32_t)(d * d);
+    e += block_err_lp_term(c, dv);
   }
   last = group_max<64>(last);
   if (lane == 0) eob[bi] = (uint16_t)last;
@@ -1001,6 +971,22 @@ __global__ __launch_bounds__(64) void quant_table_kernel(const int32_t *__restri
       if (group_max<64>(dropped)) last = 0;
     }
   }
+  if (lane == 0) *eob = (uint16_t)last;
+}
+// av1_quantize_lp with the caller's scan tables (the rtcd-signature aomhip_quantize_lp): quant_lp_kernel's arithmetic, eob = 1 + max iscan[rc]
+// over non-zero levels.  One wavefront per call.
+__global__ __launch_bounds__(64) void quant_lp_table_kernel(const int16_t *__restrict__ coeff, int n, QuantArgs qa, const int16_t *__restrict__ iscan,
+                                                            int16_t *__restrict__ qcoeff, int16_t *__restrict__ dqcoeff, uint16_t *__restrict__ eob) {
+  const int lane = threadIdx.x;
+  int last = 0;
+  for (int rc = lane; rc < n; rc += 64) {
+    const int ac = rc != 0;
+    int16_t qv, dv;
+    if (quantize_one_lp(coeff[rc], qa.round[ac], qa.quant[ac], qa.dequant[ac], &qv, &dv)) last = max(last, (int)iscan[rc] + 1);
+    qcoeff[rc] = qv;
+    dqcoeff[rc] = dv;
+  }
+  last = group_max<64>(last);
   if (lane == 0) *eob = (uint16_t)last;
 }
 
@@ -1471,19 +1457,25 @@ int aomhip_subtract_xform_quant_qm_batch(aomhip_ctx *ctx, const aomhip_planes *s
 }
 
 
-// The rtcd-signature quantisers (aom_dsp/aom_dsp_rtcd_defs.pl:653-693): host pointers, one launch, synchronous.
-// log_scale 0 / 1 / 2 = aom_quantize_b / _32x32 / _64x64; is_hbd: the aom_highbd_ family; adaptive: the _adaptive family.
-// A failed call records the sticky status (aomhip_status()), zeroes the outputs and returns.
-void aomhip_quantize_b_any(const int32_t *coeff_ptr, intptr_t n_coeffs, const int16_t *zbin_ptr, const int16_t *round_ptr,
-                           const int16_t *quant_ptr, const int16_t *quant_shift_ptr, int32_t *qcoeff_ptr, int32_t *dqcoeff_ptr,
-                           const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan, int log_scale,
-                           int is_hbd, int adaptive) {
-  (void)scan;
+// The rtcd-signature quantisers (aom_dsp/aom_dsp_rtcd_defs.pl:653-693; av1/common/av1_rtcd_defs.pl:334-347): host pointers, one launch,
+// synchronous, on the caller's iscan.  log_scale 0 / 1 / 2 = _ / _32x32 / _64x64; is_hbd: the highbd family; adaptive: the _adaptive family;
+// quant_kind AOMHIP_QUANT_FP: the av1_quantize_fp family (qp carries round_fp / quant_fp).  A failed call records the sticky status
+// (aomhip_status()), zeroes the outputs and returns.
+// zbin_ptr / quant_shift_ptr may be NULL for the fp family (not read there).
+static void quantize_table_call(const char *who, const int32_t *coeff_ptr, intptr_t n_coeffs, const int16_t *zbin_ptr, const int16_t *round_ptr,
+                                const int16_t *quant_ptr, const int16_t *quant_shift_ptr, const int16_t *dequant_ptr, int32_t *qcoeff_ptr,
+                                int32_t *dqcoeff_ptr, uint16_t *eob_ptr, const int16_t *iscan, int log_scale, int is_hbd, int adaptive,
+                                int quant_kind) {
+  auto fail = [who](const char *stage, int status) {
+    char what[64];
+    snprintf(what, sizeof(what), "%s %s", who, stage);
+    note_failure(what, status);
+  };
   *eob_ptr = 0;
   // (range check BEFORE anything is sized by n_coeffs: an invalid count zeroes *eob_ptr only and touches no block memory)
   if (n_coeffs <= 0 || n_coeffs > 4096 || log_scale < 0 || log_scale > 2) {
-    set_error("aomhip_quantize_b: n_coeffs %ld / log_scale %d unsupported", (long)n_coeffs, log_scale);
-    return note_failure("aomhip_quantize_b", AOMHIP_ERR_INVALID);
+    set_error("%s: n_coeffs %ld / log_scale %d unsupported", who, (long)n_coeffs, log_scale);
+    return note_failure(who, AOMHIP_ERR_INVALID);
   }
   const size_t n = (size_t)n_coeffs;
   memset(qcoeff_ptr, 0, n * 4);
@@ -1493,16 +1485,16 @@ void aomhip_quantize_b_any(const int32_t *coeff_ptr, intptr_t n_coeffs, const in
   const size_t isc_off = n * 4, q_off = (isc_off + n * 2 + 15) & ~(size_t)15, dq_off = q_off + n * 4, e_off = dq_off + n * 4;
   const size_t total = e_off + 16;
   char *h = static_cast<char *>(pinned(ctx, total)), *d = static_cast<char *>(scratch(ctx, total));
-  if (!h || !d) return note_failure("aomhip_quantize_b scratch", AOMHIP_ERR_NOMEM);
+  if (!h || !d) return fail("scratch", AOMHIP_ERR_NOMEM);
   memcpy(h, coeff_ptr, n * 4);
   memcpy(h + isc_off, iscan, n * 2);
-  if (hipMemcpyAsync(d, h, q_off, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return note_failure("aomhip_quantize_b H2D");
+  if (hipMemcpyAsync(d, h, q_off, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return fail("H2D", AOMHIP_ERR_HIP);
   aomhip_quant_params qp;
   for (int i = 0; i < 2; ++i) {
-    qp.zbin[i] = zbin_ptr[i]; qp.round[i] = round_ptr[i]; qp.quant[i] = quant_ptr[i];
-    qp.quant_shift[i] = quant_shift_ptr[i]; qp.dequant[i] = dequant_ptr[i];
+    qp.zbin[i] = zbin_ptr ? zbin_ptr[i] : 0; qp.round[i] = round_ptr[i]; qp.quant[i] = quant_ptr[i];
+    qp.quant_shift[i] = quant_shift_ptr ? quant_shift_ptr[i] : 1; qp.dequant[i] = dequant_ptr[i];
   }
-  const QuantArgs qa = to_args(&qp);
+  const QuantArgs qa = to_args(&qp, quant_kind);
   const int32_t *dc = reinterpret_cast<const int32_t *>(d);
   const int16_t *di = reinterpret_cast<const int16_t *>(d + isc_off);
   int32_t *dq = reinterpret_cast<int32_t *>(d + q_off), *ddq = reinterpret_cast<int32_t *>(d + dq_off);
@@ -1515,12 +1507,63 @@ void aomhip_quantize_b_any(const int32_t *coeff_ptr, intptr_t n_coeffs, const in
   else { if (adaptive) AOMHIP_QT_LS(false, true); else AOMHIP_QT_LS(false, false); }
 #undef AOMHIP_QT_LS
 #undef AOMHIP_QT
-  if (hipGetLastError() != hipSuccess) return note_failure("aomhip_quantize_b launch");
+  if (hipGetLastError() != hipSuccess) return fail("launch", AOMHIP_ERR_HIP);
   if (hipMemcpyAsync(h + q_off, d + q_off, total - q_off, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess)
-    return note_failure("aomhip_quantize_b D2H");
+    return fail("D2H", AOMHIP_ERR_HIP);
   memcpy(qcoeff_ptr, h + q_off, n * 4);
   memcpy(dqcoeff_ptr, h + dq_off, n * 4);
+  *eob_ptr = *reinterpret_cast<const uint16_t *>(h + e_off);
+}
+
+void aomhip_quantize_b_any(const int32_t *coeff_ptr, intptr_t n_coeffs, const int16_t *zbin_ptr, const int16_t *round_ptr,
+                           const int16_t *quant_ptr, const int16_t *quant_shift_ptr, int32_t *qcoeff_ptr, int32_t *dqcoeff_ptr,
+                           const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan, int log_scale,
+                           int is_hbd, int adaptive) {
+  (void)scan;
+  quantize_table_call("aomhip_quantize_b", coeff_ptr, n_coeffs, zbin_ptr, round_ptr, quant_ptr, quant_shift_ptr, dequant_ptr, qcoeff_ptr, dqcoeff_ptr,
+                      eob_ptr, iscan, log_scale, is_hbd, adaptive, AOMHIP_QUANT_B);
+}
+
+// av1_quantize_fp* / av1_highbd_quantize_fp (av1/encoder/av1_quantize.c:36-69,181-300): the zbin / quant_shift rows are not read
+void aomhip_quantize_fp_any(const int32_t *coeff_ptr, intptr_t n_coeffs, const int16_t *round_ptr, const int16_t *quant_ptr, int32_t *qcoeff_ptr,
+                            int32_t *dqcoeff_ptr, const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *iscan, int log_scale, int is_hbd) {
+  quantize_table_call("aomhip_quantize_fp", coeff_ptr, n_coeffs, nullptr, round_ptr, quant_ptr, nullptr, dequant_ptr, qcoeff_ptr, dqcoeff_ptr,
+                      eob_ptr, iscan, log_scale, is_hbd, 0, AOMHIP_QUANT_FP);
+}
+
+// av1_quantize_lp (av1/encoder/av1_quantize.c:212-240) on the caller's iscan: int16 coefficients in and out
+void aomhip_quantize_lp_any(const int16_t *coeff_ptr, intptr_t n_coeffs, const int16_t *round_ptr, const int16_t *quant_ptr, int16_t *qcoeff_ptr,
+                            int16_t *dqcoeff_ptr, const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *iscan) {
+  const char *who = "aomhip_quantize_lp";
+  *eob_ptr = 0;
+  if (n_coeffs <= 0 || n_coeffs > 4096) {
+    set_error("%s: n_coeffs %ld unsupported", who, (long)n_coeffs);
+    return note_failure(who, AOMHIP_ERR_INVALID);
+  }
+  const size_t n = (size_t)n_coeffs;
+  memset(qcoeff_ptr, 0, n * 2);
+  memset(dqcoeff_ptr, 0, n * 2);
+  aomhip_ctx *ctx = default_ctx();
+  if (!ctx) return;
+  const size_t isc_off = (n * 2 + 15) & ~(size_t)15, q_off = (isc_off + n * 2 + 15) & ~(size_t)15, dq_off = q_off + n * 2;
+  const size_t e_off = (dq_off + n * 2 + 15) & ~(size_t)15, total = e_off + 16;
+  char *h = static_cast<char *>(pinned(ctx, total)), *d = static_cast<char *>(scratch(ctx, total));
+  if (!h || !d) return note_failure(who, AOMHIP_ERR_NOMEM);
+  memcpy(h, coeff_ptr, n * 2);
+  memcpy(h + isc_off, iscan, n * 2);
+  if (hipMemcpyAsync(d, h, q_off, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return note_failure(who);
+  aomhip_quant_params qp = { { 0, 0 }, { round_ptr[0], round_ptr[1] }, { quant_ptr[0], quant_ptr[1] }, { 1, 1 },
+                             { dequant_ptr[0], dequant_ptr[1] } };
+  hipLaunchKernelGGL(quant_lp_table_kernel, dim3(1), dim3(64), 0, ctx->stream, reinterpret_cast<const int16_t *>(d), (int)n, to_args(&qp),
+                     reinterpret_cast<const int16_t *>(d + isc_off), reinterpret_cast<int16_t *>(d + q_off), reinterpret_cast<int16_t *>(d + dq_off),
+                     reinterpret_cast<uint16_t *>(d + e_off));
+  if (hipGetLastError() != hipSuccess) return note_failure(who);
+  if (hipMemcpyAsync(h + q_off, d + q_off, total - q_off, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return note_failure(who);
+  memcpy(qcoeff_ptr, h + q_off, n * 2);
+  memcpy(dqcoeff_ptr, h + dq_off, n * 2);
   *eob_ptr = *reinterpret_cast<const uint16_t *>(h + e_off);
 }
 

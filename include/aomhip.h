@@ -421,6 +421,15 @@ int aomhip_quantize_fp_qm_batch(aomhip_ctx *ctx, const int32_t *d_coeff, int tx_
  * av1_block_error_lp_c (av1/encoder/rdopt.c:650-660) of (coeff, dqcoeff), what block_yrd takes next (nonrd_pickmode.c). */
 int aomhip_quantize_lp_batch(aomhip_ctx *ctx, const int16_t *d_coeff, int tx_size, const aomhip_txb *d_blocks, int n_blocks, int uniform_tx_type,
                              const aomhip_quant_params *qparams, int16_t *d_qcoeff, int16_t *d_dqcoeff, uint16_t *d_eob, int64_t *d_err);
+/* The transform-domain distortion on coefficients that are already in device memory: av1_block_error_c / av1_highbd_block_error_c
+ * (av1/encoder/rdopt.c:635-682) per block, for outputs that carry no fused error (the matrix and adaptive quantisers, a separate lp pass).
+ * Block i's coefficients at d_coeff + i * n_coeffs and d_dqcoeff + i * n_coeffs (1 <= n_coeffs <= 4096).  d_out[2 i] = error,
+ * d_out[2 i + 1] = ssz: the d_block_error layout of aomhip_xform_quant_ex_batch.  !is_hbd: the low-bd form, whose products are 32-bit and
+ * wrap as in the compiled reference (bit_depth not read); is_hbd: the highbd form, both sums rounded by 2 * (bit_depth - 8) bits.
+ * aomhip_block_error_lp_batch: av1_block_error_lp_c (:650-660) on int16 coefficients, one int64 per block (32-bit products, wrapping). */
+int aomhip_block_error_batch(aomhip_ctx *ctx, const int32_t *d_coeff, const int32_t *d_dqcoeff, int n_coeffs, int n_blocks, int is_hbd,
+                             int bit_depth, int64_t *d_out);
+int aomhip_block_error_lp_batch(aomhip_ctx *ctx, const int16_t *d_coeff, const int16_t *d_dqcoeff, int n_coeffs, int n_blocks, int64_t *d_out);
 int aomhip_xform_quant_qm_batch(aomhip_ctx *ctx, const int16_t *d_residual, int residual_stride, int tx_size, const aomhip_txb *d_blocks,
                                 int n_blocks, int grid_cols, int uniform_tx_type, const aomhip_quant_params *qparams, int is_hbd,
                                 const uint8_t *d_qm, const uint8_t *d_iqm, int32_t *d_coeff, int32_t *d_qcoeff, int32_t *d_dqcoeff, uint16_t *d_eob);
@@ -1742,6 +1751,115 @@ typedef struct aomhip_rtcd_table {
   aomhip_variance_vtable block_fns[3][22];
 } aomhip_rtcd_table;
 int aomhip_rtcd(aomhip_rtcd_table *table);
+
+/* ---- the av1_rtcd transform / quantisation surface: the TxfmParam dispatchers the encoder calls, fp / lp, block error ---- */
+
+/* TxfmParam (aom_dsp/txfm_common.h:89-101) byte for byte: TX_TYPE, TX_SIZE and TxSetType are UENUM1BYTE (uint8_t).  The
+ * entry points below take it as `const void *` / `void *` like their prototypes (av1_rtcd_defs.pl spells TxfmParam) and read it as
+ * this struct.  tx_set_type is not read: tx-set membership is the caller's contract (the reference only asserts it). */
+typedef struct aomhip_txfm_param {
+  uint8_t tx_type;     /* TX_TYPE 0..15 */
+  uint8_t tx_size;     /* TX_SIZE 0..18 (av1/common/enums.h) */
+  int lossless;        /* the 4x4 Walsh-Hadamard pair: TX_4X4 and DCT_DCT only */
+  int bd;              /* 8, 10, 12 */
+  int is_hbd;
+  uint8_t tx_set_type; /* TxSetType */
+  int eob;             /* inverse only; read only by the lossless 4x4 case */
+} aomhip_txfm_param;
+#if defined(__cplusplus)
+#define AOMHIP_STATIC_ASSERT(cond, name) static_assert(cond, #name)
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+#define AOMHIP_STATIC_ASSERT(cond, name) _Static_assert(cond, #name)
+#else
+#define AOMHIP_STATIC_ASSERT(cond, name) typedef char name[(cond) ? 1 : -1]
+#endif
+AOMHIP_STATIC_ASSERT(offsetof(aomhip_txfm_param, tx_type) == 0 && offsetof(aomhip_txfm_param, tx_size) == 1 &&
+                         offsetof(aomhip_txfm_param, lossless) == 4 && offsetof(aomhip_txfm_param, bd) == 8 &&
+                         offsetof(aomhip_txfm_param, is_hbd) == 12 && offsetof(aomhip_txfm_param, tx_set_type) == 16 &&
+                         offsetof(aomhip_txfm_param, eob) == 20 && sizeof(aomhip_txfm_param) == 24,
+                     aomhip_txfm_param_layout_is_TxfmParam);
+
+/* Conventions of this group (host pointers, synchronous, one launch per call, the batched entry points' device code).  Inputs are
+ * checked before anything is written through them: tx_size < 19, tx_type < 16 and a pair the transform exists for (ADST <= 16 points,
+ * identity <= 32, 64-point sizes DCT_DCT only), bd in {8, 10, 12}, lossless only with TX_4X4 + DCT_DCT, n_coeffs in 1..4096.  A failed
+ * check records AOMHIP_ERR_INVALID in the sticky status with a message naming the value (aomhip_last_error()).  On any failure:
+ * coefficient-like outputs (coeff, qcoeff, dqcoeff, *eob) are zeroed where their extent is known, pixels are left untouched, and a block
+ * error returns the losing distortion AOMHIP_FAILED_BLOCK_ERROR (also written to *ssz): 0 would make the failed block win the RD search,
+ * and this value survives the callers' << 4 and * (1 << RDDIV_BITS) (av1/encoder/rdopt.c, rd.h) without overflowing int64. */
+#define AOMHIP_FAILED_BLOCK_ERROR ((int64_t)1 << 50)
+
+/* av1_inv_txfm_add (av1/common/idct.c:281-302; av1_rtcd_defs.pl:140): 8-bit pixels, txfm_param->bd must be 8 (anything else records
+ * AOMHIP_ERR_INVALID).  av1_highbd_inv_txfm_add (idct.c:212-279; :139) and the per-size av1_highbd_inv_txfm_add_WxH (:143-177; the
+ * reference declares no 16x16 proto, the library has one so that the installer's table is indexed by TX_SIZE): `dest` is
+ * CONVERT_TO_BYTEPTR-encoded (aom_ports/mem.h:79-80) uint16 pixels.  The per-size forms take their size from their name, not from
+ * txfm_param->tx_size (as the reference's do).  No eob early-out (that is av1_inverse_transform_block's): eob is read only by the
+ * lossless 4x4 case, av1_highbd_iwht4x4_add (idct.c:34-41): _16_add when eob > 1, else _1_add (eob 0 included). */
+void aomhip_inv_txfm_add(const int32_t *dqcoeff, uint8_t *dst, int stride, const void *txfm_param);
+void aomhip_highbd_inv_txfm_add(const int32_t *input, uint8_t *dest, int stride, const void *txfm_param);
+#define AOMHIP_DECL_HBD_INV(W, H) void aomhip_highbd_inv_txfm_add_##W##x##H(const int32_t *input, uint8_t *dest, int stride, const void *txfm_param);
+AOMHIP_RTCD_TX_SIZES(AOMHIP_DECL_HBD_INV)
+#undef AOMHIP_DECL_HBD_INV
+/* av1_highbd_iwht4x4_1_add / _16_add (av1_rtcd_defs.pl:217-218; av1/common/av1_inv_txfm2d.c:20-114): CONVERT_TO_BYTEPTR `dest` */
+void aomhip_highbd_iwht4x4_1_add(const int32_t *input, uint8_t *dest, int dest_stride, int bd);
+void aomhip_highbd_iwht4x4_16_add(const int32_t *input, uint8_t *dest, int dest_stride, int bd);
+
+/* av1_lowbd_fwd_txfm (av1/encoder/hybrid_fwd_txfm.c:239-242 -> av1_highbd_fwd_txfm :244-313): txfm_param->lossless selects av1_fwht4x4,
+ * every other block av1_fwd_txfm2d_WxH.  Writes aomhip_tx_max_eob(tx_size) coefficients (reference layout), what every caller reads.
+ * av1_fwht4x4 (hybrid_fwd_txfm.c:24-76; :223): the lossless forward transform alone, 16 coefficients. */
+void aomhip_lowbd_fwd_txfm(const int16_t *src_diff, int32_t *coeff, int diff_stride, void *txfm_param);
+void aomhip_fwht4x4(const int16_t *input, int32_t *output, int stride);
+/* av1_round_shift_array (av1/common/av1_txfm.c:71-86; av1_rtcd_defs.pl:269) in place: round_shift by `bit` when bit > 0, the left shift
+ * clamped to int32 in 64 bits when bit < 0.  0 <= size <= 4096, -31 <= bit <= 31. */
+void aomhip_round_shift_array(int32_t *arr, int size, int bit);
+
+/* av1_block_error / av1_block_error_lp / av1_highbd_block_error (av1/encoder/rdopt.c:635-682; av1_rtcd_defs.pl): the low-bd forms
+ * multiply in 32 bits and wrap like the compiled reference, the highbd form rounds both sums by 2 * (bd - 8) bits (bd in {8, 10, 12}). */
+int64_t aomhip_block_error(const int32_t *coeff, const int32_t *dqcoeff, intptr_t block_size, int64_t *ssz);
+int64_t aomhip_block_error_lp(const int16_t *coeff, const int16_t *dqcoeff, intptr_t block_size);
+int64_t aomhip_highbd_block_error(const int32_t *coeff, const int32_t *dqcoeff, intptr_t block_size, int64_t *ssz, int bd);
+
+/* av1_quantize_fp / _32x32 / _64x64 (log_scale 0 / 1 / 2) and av1_highbd_quantize_fp (log_scale an argument, 0..2), av1/encoder/
+ * av1_quantize.c:36-69,181-300 (av1_rtcd_defs.pl:334-345): round_ptr / quant_ptr are round_fp / quant_fp, zbin_ptr and quant_shift_ptr are
+ * not read.  av1_quantize_lp (:212-240; :347): int16 coefficients.  Like aomhip_quantize_b, they run on the caller's `iscan` (eob = 1 +
+ * the largest iscan position of a non-zero level), which must be the inverse of `scan`. */
+AOMHIP_DECL_QUANTIZE_B(aomhip_quantize_fp);
+AOMHIP_DECL_QUANTIZE_B(aomhip_quantize_fp_32x32);
+AOMHIP_DECL_QUANTIZE_B(aomhip_quantize_fp_64x64);
+void aomhip_highbd_quantize_fp(const int32_t *coeff_ptr, intptr_t count, const int16_t *zbin_ptr, const int16_t *round_ptr,
+                               const int16_t *quant_ptr, const int16_t *quant_shift_ptr, int32_t *qcoeff_ptr, int32_t *dqcoeff_ptr,
+                               const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan, int log_scale);
+void aomhip_quantize_lp(const int16_t *coeff_ptr, intptr_t n_coeffs, const int16_t *round_ptr, const int16_t *quant_ptr, int16_t *qcoeff_ptr,
+                        int16_t *dqcoeff_ptr, const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan);
+
+/* cdef_copy_rect8_8bit_to_16bit / cdef_copy_rect8_16bit_to_16bit (av1/common/cdef.c:70-90; av1_rtcd_defs.pl): a width x height
+ * rectangle into CDEF's 16-bit working buffer.  0 <= width, height <= 1024. */
+void aomhip_cdef_copy_rect8_8bit_to_16bit(uint16_t *dst, int dstride, const uint8_t *src, int sstride, int width, int height);
+void aomhip_cdef_copy_rect8_16bit_to_16bit(uint16_t *dst, int dstride, const uint16_t *src, int sstride, int width, int height);
+
+/* The second installer, for the av1_rtcd globals of the list above (av1_rtcd_defs.pl): same conventions as
+ * aomhip_rtcd -- memset, AOMHIP_ERR_NO_DEVICE and an all-NULL table without a GPU.  36 pointers; highbd_inv_txfm_add_sz by TX_SIZE. */
+typedef void (*aomhip_inv_txfm_add_fn)(const int32_t *input, uint8_t *dest, int stride, const void *txfm_param);
+typedef void (*aomhip_iwht4x4_add_fn)(const int32_t *input, uint8_t *dest, int dest_stride, int bd);
+typedef struct aomhip_rtcd_av1_table {
+  aomhip_inv_txfm_add_fn inv_txfm_add, highbd_inv_txfm_add;
+  aomhip_inv_txfm_add_fn highbd_inv_txfm_add_sz[19];
+  aomhip_iwht4x4_add_fn highbd_iwht4x4_1_add, highbd_iwht4x4_16_add;
+  void (*lowbd_fwd_txfm)(const int16_t *src_diff, int32_t *coeff, int diff_stride, void *txfm_param);
+  void (*fwht4x4)(const int16_t *input, int32_t *output, int stride);
+  void (*round_shift_array)(int32_t *arr, int size, int bit);
+  int64_t (*block_error)(const int32_t *coeff, const int32_t *dqcoeff, intptr_t block_size, int64_t *ssz);
+  int64_t (*block_error_lp)(const int16_t *coeff, const int16_t *dqcoeff, intptr_t block_size);
+  int64_t (*highbd_block_error)(const int32_t *coeff, const int32_t *dqcoeff, intptr_t block_size, int64_t *ssz, int bd);
+  aomhip_quantize_b_fn quantize_fp, quantize_fp_32x32, quantize_fp_64x64;
+  void (*highbd_quantize_fp)(const int32_t *coeff_ptr, intptr_t count, const int16_t *zbin_ptr, const int16_t *round_ptr,
+                             const int16_t *quant_ptr, const int16_t *quant_shift_ptr, int32_t *qcoeff_ptr, int32_t *dqcoeff_ptr,
+                             const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan, int log_scale);
+  void (*quantize_lp)(const int16_t *coeff_ptr, intptr_t n_coeffs, const int16_t *round_ptr, const int16_t *quant_ptr, int16_t *qcoeff_ptr,
+                      int16_t *dqcoeff_ptr, const int16_t *dequant_ptr, uint16_t *eob_ptr, const int16_t *scan, const int16_t *iscan);
+  void (*cdef_copy_rect8_8bit_to_16bit)(uint16_t *dst, int dstride, const uint8_t *src, int sstride, int width, int height);
+  void (*cdef_copy_rect8_16bit_to_16bit)(uint16_t *dst, int dstride, const uint16_t *src, int sstride, int width, int height);
+} aomhip_rtcd_av1_table;
+int aomhip_rtcd_av1(aomhip_rtcd_av1_table *table);
 
 #ifdef __cplusplus
 }
