@@ -187,6 +187,9 @@ _protos = {
     "aomhip_estimate_txfm_yrd_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "aomhip_variance_sb_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp]),
     "aomhip_sub_pixel_variance_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
+    "aomhip_sub_pixel_variance_sb_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp]),
+    "aomhip_debug_subpel_sb_fallbacks": (C.c_int, [_vp]),
+    "aomhip_debug_subpel_sb_launch_info": (C.c_int, [_vp, _vp]),
     "aomhip_variance": (C.c_uint, [_vp, _i, _vp, _i, _i, _i, C.POINTER(C.c_uint)]),
     "aomhip_mse": (C.c_uint, [_vp, _i, _vp, _i, _i, _i, C.POINTER(C.c_uint)]),
     "aomhip_get_var": (None, [_vp, _i, _vp, _i, _i, _i, C.POINTER(C.c_uint), C.POINTER(C.c_int)]),
@@ -619,6 +622,25 @@ class Context:
         check(lib.aomhip_variance_sb_batch(self.h, C.byref(src), C.byref(ref), first_frame, n_frames, bw, bh, sb_w, sb_h, rng, n_buckets, d_groups,
                                            d_group_off, n_groups, group_frame_stride, d_var_groups, d_sse_groups, d_cands, d_cand_off, n_cands,
                                            cand_frame_stride, d_var_cands, d_sse_cands), "aomhip_variance_sb_batch")
+
+    def sub_pixel_variance_sb_batch(self, src, ref, first_frame, n_frames, bw, bh, sb_w, sb_h, rng, n_buckets, d_cands=None, d_cand_off=None,
+                                    n_cands=0, cand_frame_stride=0, d_var=None, d_sse=None):
+        check(lib.aomhip_sub_pixel_variance_sb_batch(self.h, C.byref(src), C.byref(ref), first_frame, n_frames, bw, bh, sb_w, sb_h, rng, n_buckets,
+                                                     d_cands, d_cand_off, n_cands, cand_frame_stride, d_var, d_sse),
+              "aomhip_sub_pixel_variance_sb_batch")
+
+    def debug_subpel_sb_fallbacks(self):
+        """entries the most recent sub_pixel_variance_sb_batch served from global memory instead of LDS"""
+        n = lib.aomhip_debug_subpel_sb_fallbacks(self.h)
+        if n < 0:
+            raise AomHipError("aomhip_debug_subpel_sb_fallbacks: " + lib.aomhip_last_error().decode())
+        return n
+
+    def debug_subpel_sb_launch_info(self):
+        """shape of the most recent sub_pixel_variance_sb_batch launch: LDS bytes, workgroups, slice capacity, registers and scratch per lane"""
+        out = (C.c_int32 * 5)()
+        check(lib.aomhip_debug_subpel_sb_launch_info(self.h, out), "aomhip_debug_subpel_sb_launch_info")
+        return dict(zip(("lds_bytes", "workgroups", "slice_entries", "registers_per_lane", "scratch_bytes_per_lane"), list(out)))
 
     def variance_batch(self, src, ref, first_frame, n_frames, bw, bh, d_cands, n, stride, d_var, d_sse, subpel=False):
         f = lib.aomhip_sub_pixel_variance_batch if subpel else lib.aomhip_variance_batch

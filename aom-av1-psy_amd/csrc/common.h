@@ -35,6 +35,10 @@ struct aomhip_ctx {
   // and joined back into `stream` with the two events inside the call, so callers -- and a graph capture of `stream` -- see one stream
   hipStream_t side_stream;
   hipEvent_t ev_fork, ev_join;
+  // aomhip_sub_pixel_variance_sb_batch's test / measurement support: the device word its kernel counts global-memory entries in (allocated on
+  // first use, zeroed on the stream before every launch) and the shape of the most recent launch (aomhip_debug_subpel_sb_launch_info)
+  unsigned *d_subpel_fallbacks;
+  int subpel_launch_info[5];
 };
 
 namespace aomhip {

@@ -230,6 +230,7 @@ void aomhip_ctx_destroy(aomhip_ctx *ctx) {
   if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
   if (ctx->d_work) (void)hipFree(ctx->d_work);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
+  if (ctx->d_subpel_fallbacks) (void)hipFree(ctx->d_subpel_fallbacks);
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   (void)hipEventDestroy(ctx->ev0);

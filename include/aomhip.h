@@ -217,8 +217,9 @@ int aomhip_sad_sb_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_
 /* aom_varianceWxH / aom_highbd_{10,12}_varianceWxH (aom_dsp/variance.c:56-163,383-420) through the SAME strip walk: the lists, the buckets, the
  * range contract and the fall-backs are aomhip_sad_sb_batch's (a candidate outside its window is still evaluated, from memory), the results
  * per candidate are the variance (d_var_*) and *sse (d_sse_*): d_var_groups / d_sse_groups hold 4 values per group, d_var_cands / d_sse_cands
- * one per candidate; diff = src - ref.  Blocks of at most 256 pixels (4x4 .. 16x16, 8x32, 32x8: the sums are 32-bit); larger blocks and
- * sub-pixel positions: aomhip_variance_batch / aomhip_sub_pixel_variance_batch.  Round 6: on the Mode-A rings the direct kernel is bound by
+ * one per candidate; diff = src - ref.  Blocks of at most 256 pixels (4x4 .. 16x16, 8x32, 32x8: the sums are 32-bit); larger blocks:
+ * aomhip_variance_batch; sub-pixel positions: aomhip_sub_pixel_variance_sb_batch below for blocks of at most 32x32 (the same buckets, one
+ * flat list), aomhip_sub_pixel_variance_batch otherwise.  Round 6: on the Mode-A rings the direct kernel is bound by
  * the L1 fill path (every lane pulls its 16-byte row out of a different line); here every reference row enters LDS once. */
 int aomhip_variance_sb_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *ref, int first_frame, int n_frames, int bw, int bh,
                              int sb_w, int sb_h, int range, int n_buckets, const aomhip_sad_x4d_cand *d_groups,
@@ -271,6 +272,38 @@ int aomhip_variance_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhi
 int aomhip_sub_pixel_variance_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *ref,
                                     int first_frame, int n_frames, int bw, int bh, const aomhip_var_cand *d_cands,
                                     int n_cands, int64_t cand_frame_stride, uint32_t *d_var, uint32_t *d_sse);
+
+/* aom_sub_pixel_varianceWxH / aom_highbd_{10,12}_sub_pixel_varianceWxH for work lists bucketed by superblock: the results of
+ * aomhip_sub_pixel_variance_batch on the same list, bit for bit, for every (xoff, yoff) in 0..7 x 0..7 ((0, 0), (x, 0) and (0, y) run both
+ * bilinear passes with the {128, 0} taps, as the reference does) and 8/10/12-bit planes; diff = interpolated ref - src.
+ *   d_cands is ONE flat list of aomhip_var_cand, bucketed by the cell the SOURCE block starts in exactly as aomhip_sad_sb_batch buckets its
+ *   lists: cells of sb_w x sb_h pixels in raster order, n_buckets must equal their number, bucket b = entries [d_bucket_offsets[b],
+ *   d_bucket_offsets[b + 1]).  Frames, cand_frame_stride (0 = one list shared by all frames; the offsets are always shared) and the output
+ *   indexing d_var / d_sse[f_rel * n_cands + i] are aomhip_variance_sb_batch's.
+ *   Block sizes: the 14 sizes with both sides <= 32; larger blocks are refused (use aomhip_sub_pixel_variance_batch).
+ *   Range contract (the same sentence as for SAD): an entry whose source block lies in its cell and whose INTEGER reference position
+ *   (rx, ry) lies within `range` of the cell ([cell_x0 - range, cell_x0 + sb_w + range) x likewise in y for the W x H block at (rx, ry))
+ *   is served from LDS whatever its offset -- the staged window is one column and one row larger than the SAD kernel's, the
+ *   (W + 1) x (H + 1) footprint of the bilinear taps.  Any other entry (beyond `range`, in the wrong bucket, a window clipped by the end of
+ *   the plane's allocation) is still evaluated exactly, from global memory: slower, never wrong.  Positions aomhip_sub_pixel_variance_batch
+ *   accepts are accepted here; nothing is validated or rejected per entry.
+ *   A persistent workgroup walks one column of cells of one frame with the window in an LDS ring of sb_h + 2 range + 1 rows of
+ *   sb_w + 2 range + 1 pixels (each step brings in the sb_h new rows), one source cell and a slice of the list.  Arguments that cannot
+ *   work -- a list without offsets, d_var or d_sse NULL, n_buckets != number of cells, a window beyond the 160 KB LDS of a CU, planes
+ *   whose rows do not start on 16-byte boundaries (planes from aomhip_planes_alloc always do) -- fail before anything is launched;
+ *   n_cands == 0 is a no-op. */
+int aomhip_sub_pixel_variance_sb_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *ref, int first_frame, int n_frames,
+                                       int bw, int bh, int sb_w, int sb_h, int range, int n_buckets, const aomhip_var_cand *d_cands,
+                                       const int32_t *d_bucket_offsets, int n_cands, int64_t cand_frame_stride, uint32_t *d_var,
+                                       uint32_t *d_sse);
+/* Test support: the number of entries the most recent aomhip_sub_pixel_variance_sb_batch on THIS context served from global memory instead
+ * of LDS (summed over its frames; a device word owned by the context, zeroed on its stream before every launch).  Synchronises the
+ * context's stream; 0 before the first launch, -1 on failure. */
+int aomhip_debug_subpel_sb_fallbacks(aomhip_ctx *ctx);
+/* Measurement support: the shape of the most recent aomhip_sub_pixel_variance_sb_batch launch on this context --
+ * out[0] dynamic LDS bytes per workgroup, [1] workgroups, [2] list entries per slice (a bucket with more goes through several),
+ * [3] registers per lane and [4] scratch bytes per lane of the kernel launched, as the code object reports them. */
+int aomhip_debug_subpel_sb_launch_info(aomhip_ctx *ctx, int32_t out[5]);
 
 /* ------------------------------------------------------------------ compound / masked / OBMC table members
  * The remaining members of aom_variance_fn_ptr_t (aom_dsp/variance.h:84-103) as ONE batched call: per candidate the
