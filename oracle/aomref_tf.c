@@ -98,11 +98,42 @@ void orc_tf_build_predictor_plane(const void *ref_origin, int ref_stride, void *
     }
 }
 
+/* ORC_TF_TIE_ULPS: how close (in ulp of the double product p = exp(-scaled_error) * 1000) p must come to an integer before another
+ * conforming exp() may give weight = (int)p a different value.  scaled_error itself is a chain of single IEEE-754 operations on the
+ * same operands everywhere, so exp() and the product are the only places where two implementations may part.  Three terms:
+ *   E_HOST   glibc's exp().  The glibc manual ("Known Maximum Errors in Math Functions") gives 1 ulp for x86_64.
+ *   E_DEVICE the device library's double-precision exp().  The HIP math API documentation gives 1 ulp; the OpenCL C
+ *            specification, to which the underlying device library is written, allows a double-precision exp() 3 ulp.
+ *   the product's own rounding, 1/2 ulp on either side: 1 in all.
+ * Neither document comes with the toolchains this project builds with (the C library's manual is a separate package; the ROCm
+ * installation carries the HIP runtime API pages but not the math API's accuracy tables), so the figures above are quoted from the
+ * public documents rather than read off the installation.  To stay on the safe side of that, BOTH exp() terms take the largest
+ * figure documented for either, 3 ulp, doubled: 6.  An ulp of e = exp(-s) is worth at most 1000 / 512 < 2 ulp of p (p = 1000 e lies 9 or 10
+ * binades above e, and the ulp is measured upwards, nextafter(p, inf) - p, the larger one at a power of two), so the host's p and the
+ * device's p differ by at most 2 * (E_HOST + E_DEVICE) + 1 = 25 ulp of p, and only an integer inside that distance of the host's p
+ * can separate the two weights.  Nothing here is measured against the kernel under test. */
+#define ORC_TF_E_HOST 6
+#define ORC_TF_E_DEVICE 6
+#define ORC_TF_TIE_ULPS (2 * (ORC_TF_E_HOST + ORC_TF_E_DEVICE) + 1)
+int orc_tf_tie_ulps(void) { return ORC_TF_TIE_ULPS; }
+
+/* What a stats run collects for one block or, summed, for a frame.  hist[plane]: [0] weight == 0, [1] weight == 1000 (the frame to
+ * filter's self-weights are added elsewhere and never counted), [2 + k] k * 100 <= weight < (k + 1) * 100 for weights 1..999,
+ * [12] d_factor > 1 and weight > 0, [13] 0 < scaled_error < 7, [14] d_factor > 1, [15] all evaluations.  min_ulp[plane]: the
+ * smallest distance of exp(-scaled_error) * 1000 from an integer, in ulp of the product, over the evaluations of [13]. */
+typedef struct {
+  int64_t hist[3][ORC_TF_HIST];
+  double min_ulp[3];
+} tf_stats;
+
 /* av1_apply_temporal_filter_c (temporal_filter.c:557-712) for one block.  frame_planes[p]: pixel (0, 0) of plane p of the frame to
- * filter; pred: the block's predictors, planes one after the other (plane_w x plane_h each); accum / count likewise. */
-void orc_tf_apply_block(const void *const *frame_planes, const int *strides, int frame_w, int frame_h, int num_planes, int ss_x, int ss_y,
-                        int mb_row, int mb_col, const double *noise_levels, const int16_t *subblock_mvs, const int32_t *subblock_mses,
-                        int q_factor, int filter_strength, const void *pred, uint32_t *accum, uint16_t *count, int elem16, int bd) {
+ * filter; pred: the block's predictors, planes one after the other (plane_w x plane_h each); accum / count likewise.
+ * st (may be NULL): statistics of the weights, added to; tie_planes[p] (with st): a byte map laid out like frame_planes[p] with
+ * tie_strides[p], set to 1 where a weight lies within ORC_TF_TIE_ULPS of changing.  Neither changes what is computed. */
+static void tf_apply_block(const void *const *frame_planes, const int *strides, int frame_w, int frame_h, int num_planes, int ss_x, int ss_y,
+                           int mb_row, int mb_col, const double *noise_levels, const int16_t *subblock_mvs, const int32_t *subblock_mses,
+                           int q_factor, int filter_strength, const void *pred, uint32_t *accum, uint16_t *count, int elem16, int bd,
+                           tf_stats *st, uint8_t *const *tie_planes, const int *tie_strides) {
   enum { MBH = 32, MBW = 32, PELS = 1024, WIN = 5 };
   const int min_frame_size = frame_h < frame_w ? frame_h : frame_w;
   const double inv_factor = 1.0 / ((5 + 1) * 20);              /* TF_WINDOW_BLOCK_BALANCE_WEIGHT, TF_SEARCH_ERROR_NORM_WEIGHT */
@@ -172,9 +203,35 @@ void orc_tf_apply_block(const void *const *frame_planes, const int *strides, int
         const int idx = plane_offset + i * w + j;
         accum[idx] += (uint32_t)(weight * px(pred, elem16, idx));
         count[idx] = (uint16_t)(count[idx] + weight);
+        if (st) {
+          int64_t *hist = st->hist[plane];
+          hist[15]++;
+          if (weight == 0) hist[0]++;
+          else if (weight >= 1000) hist[1]++;
+          else hist[2 + weight / 100]++;
+          if (d_factor[subblock_idx] > 1) {
+            hist[14]++;
+            if (weight > 0) hist[12]++;
+          }
+          if (scaled_error > 0 && scaled_error < 7) {
+            const double p = exp(-scaled_error) * 1000;
+            const double ulps = fabs(p - nearbyint(p)) / (nextafter(p, INFINITY) - p);
+            hist[13]++;
+            if (ulps < st->min_ulp[plane]) st->min_ulp[plane] = ulps;
+            if (ulps <= ORC_TF_TIE_ULPS && tie_planes && tie_planes[plane])
+              tie_planes[plane][(ptrdiff_t)mb_row * h * tie_strides[plane] + mb_col * w + (ptrdiff_t)i * tie_strides[plane] + j] = 1;
+          }
+        }
       }
     plane_offset += h * w;
   }
+}
+
+void orc_tf_apply_block(const void *const *frame_planes, const int *strides, int frame_w, int frame_h, int num_planes, int ss_x, int ss_y,
+                        int mb_row, int mb_col, const double *noise_levels, const int16_t *subblock_mvs, const int32_t *subblock_mses,
+                        int q_factor, int filter_strength, const void *pred, uint32_t *accum, uint16_t *count, int elem16, int bd) {
+  tf_apply_block(frame_planes, strides, frame_w, frame_h, num_planes, ss_x, ss_y, mb_row, mb_col, noise_levels, subblock_mvs, subblock_mses,
+                 q_factor, filter_strength, pred, accum, count, elem16, bd, NULL, NULL, NULL);
 }
 
 /* tf_apply_temporal_filter_self (:407-442) */
@@ -215,13 +272,20 @@ void orc_tf_normalize_block(void *const *out_planes, const int *strides, int num
 /* av1_tf_do_filtering_row's loop (:849-905) over all blocks of a frame, after the motion search: n_frames window planes per
  * component (frame_origins[f * 3 + p]; absent frames NULL), MVs / MSEs as aomhip_tf_motion_search_frames lays them out
  * ([(f * n_blocks + i) * 4 + k]).  The blocks cover ceil(h / 32) x ceil(w / 32); the planes must hold them (aligned frame + border). */
-void orc_tf_apply_frames(const void *const *frame_origins, const int *strides, int n_frames, int filter_frame, int frame_w, int frame_h,
-                         int num_planes, int ss_x, int ss_y, const double *noise_levels, const int16_t *subblock_mvs,
-                         const int32_t *subblock_mses, int q_factor, int filter_strength, void *const *out_planes, const int *out_strides,
-                         int elem16, int bd, int threads, int block_first, int block_step) {
+/* With hist (int64 [3][ORC_TF_HIST]), min_ulp (double [3]) and tie_planes (byte maps laid out like out_planes, zeroed by the caller)
+ * the weights' statistics are collected as well (tf_stats above); all three NULL: orc_tf_apply_frames. */
+void orc_tf_apply_frames_stats(const void *const *frame_origins, const int *strides, int n_frames, int filter_frame, int frame_w, int frame_h,
+                               int num_planes, int ss_x, int ss_y, const double *noise_levels, const int16_t *subblock_mvs,
+                               const int32_t *subblock_mses, int q_factor, int filter_strength, void *const *out_planes,
+                               const int *out_strides, int elem16, int bd, int threads, int block_first, int block_step, int64_t *hist,
+                               double *min_ulp, uint8_t *const *tie_planes) {
   const int mb_rows = (frame_h + 31) / 32, mb_cols = (frame_w + 31) / 32, n_blocks = mb_rows * mb_cols;
   (void)threads;
   if (block_step < 1) block_step = 1;
+  if (hist) {
+    memset(hist, 0, sizeof(int64_t) * 3 * ORC_TF_HIST);
+    for (int p = 0; p < 3; ++p) min_ulp[p] = INFINITY;
+  }
   /* (block_first, block_step: a test may ask for every k-th block only -- blocks are independent) */
 #pragma omp parallel for num_threads(threads > 0 ? threads : 1) schedule(dynamic, 4)
   for (int b = block_first; b < n_blocks; b += block_step) {
@@ -229,8 +293,11 @@ void orc_tf_apply_frames(const void *const *frame_origins, const int *strides, i
     uint32_t accum[3 * 1024];
     uint16_t count[3 * 1024];
     uint16_t pred16[3 * 1024];
+    tf_stats st;
     memset(accum, 0, sizeof(accum));
     memset(count, 0, sizeof(count));
+    memset(&st, 0, sizeof(st));
+    for (int p = 0; p < 3; ++p) st.min_ulp[p] = INFINITY;
     for (int f = 0; f < n_frames; ++f) {
       if (!frame_origins[f * 3]) continue;
       if (f == filter_frame) {
@@ -245,10 +312,26 @@ void orc_tf_apply_frames(const void *const *frame_origins, const int *strides, i
                                        mb_col, sx, sy, mvs, elem16, bd);
           plane_offset += (32 >> sx) * (32 >> sy);
         }
-        orc_tf_apply_block(frame_origins + filter_frame * 3, strides, frame_w, frame_h, num_planes, ss_x, ss_y, mb_row, mb_col, noise_levels,
-                           mvs, mses, q_factor, filter_strength, pred16, accum, count, elem16, bd);
+        tf_apply_block(frame_origins + filter_frame * 3, strides, frame_w, frame_h, num_planes, ss_x, ss_y, mb_row, mb_col, noise_levels, mvs,
+                       mses, q_factor, filter_strength, pred16, accum, count, elem16, bd, hist ? &st : NULL, tie_planes, out_strides);
       }
     }
     orc_tf_normalize_block(out_planes, out_strides, num_planes, ss_x, ss_y, mb_row, mb_col, accum, count, elem16);
+    if (hist) {
+#pragma omp critical(orc_tf_stats)
+      for (int p = 0; p < 3; ++p) {
+        for (int k = 0; k < ORC_TF_HIST; ++k) hist[p * ORC_TF_HIST + k] += st.hist[p][k];
+        if (st.min_ulp[p] < min_ulp[p]) min_ulp[p] = st.min_ulp[p];
+      }
+    }
   }
+}
+
+void orc_tf_apply_frames(const void *const *frame_origins, const int *strides, int n_frames, int filter_frame, int frame_w, int frame_h,
+                         int num_planes, int ss_x, int ss_y, const double *noise_levels, const int16_t *subblock_mvs,
+                         const int32_t *subblock_mses, int q_factor, int filter_strength, void *const *out_planes, const int *out_strides,
+                         int elem16, int bd, int threads, int block_first, int block_step) {
+  orc_tf_apply_frames_stats(frame_origins, strides, n_frames, filter_frame, frame_w, frame_h, num_planes, ss_x, ss_y, noise_levels,
+                            subblock_mvs, subblock_mses, q_factor, filter_strength, out_planes, out_strides, elem16, bd, threads, block_first,
+                            block_step, NULL, NULL, NULL);
 }

@@ -159,11 +159,46 @@ def build_inter_pred(ref_b, border, width, height, w, h, blocks, mvs, filter_x=0
     return out
 
 
+TF_HIST = 16   # aomref.h ORC_TF_HIST
+
+
+def tf_tie_ulps():
+    """aomref_tf.c ORC_TF_TIE_ULPS: the distance (ulp of exp(-scaled_error) * 1000) from an integer inside which near_tie is set."""
+    lib.orc_tf_tie_ulps.restype = C.c_int
+    return lib.orc_tf_tie_ulps()
+
+
+class TfWeightStats:
+    """The pixel weights, weight = (int)(exp(-scaled_error) * 1000), of one tf_apply_frames(..., stats=True) run, per plane; an
+    evaluation is one (pixel, window frame) pair, the frame to filter's own weights of 1000 are not among them.
+      zero[p], full[p]   evaluations with weight == 0 / == 1000
+      buckets[p][k]      evaluations with k * 100 <= weight < (k + 1) * 100 among the weights 1..999 (k = 0..9)
+      far_live[p]        evaluations with d_factor > 1 whose weight is not 0;   far[p]: all with d_factor > 1
+      open_[p]           evaluations with 0 < scaled_error < 7;   total[p]: all evaluations
+      min_tie_ulps[p]    the smallest distance of exp(-scaled_error) * 1000 from an integer over those, in ulp of the product
+      near_tie[p]        bool map shaped like the returned plane: some evaluation of the pixel came within tf_tie_ulps() of an integer,
+                         so that another conforming exp() may give that weight, and with it the pixel, another value"""
+
+    def __init__(self, hist, min_ulp, near_tie):
+        self.hist = hist
+        self.zero, self.full, self.buckets = hist[:, 0].copy(), hist[:, 1].copy(), hist[:, 2:12].copy()
+        self.far_live, self.open_, self.far, self.total = hist[:, 12].copy(), hist[:, 13].copy(), hist[:, 14].copy(), hist[:, 15].copy()
+        self.mid = self.buckets.sum(axis=1)
+        self.min_tie_ulps = min_ulp
+        self.near_tie = near_tie
+
+    def summary(self):
+        return "; ".join("p%d: 0:%d mid:%d 1000:%d buckets:%s far_live:%d min_tie:%.3g ulp" % (
+            p, self.zero[p], self.mid[p], self.full[p], ",".join(str(int(v)) for v in self.buckets[p]), self.far_live[p], self.min_tie_ulps[p])
+            for p in range(len(self.zero)))
+
+
 def tf_apply_frames(planes_b, border, width, height, filter_frame, mvs, mses, noise_levels, q_factor, filter_strength, bd=8, ss_x=0, ss_y=0,
-                    present=None, threads=8, block_first=0, block_step=1):
+                    present=None, threads=8, block_first=0, block_step=1, stats=False):
     """oracle/aomref_tf.c orc_tf_apply_frames.  planes_b: per component (1 or 3) a list of border-extended frames of the window
     (every plane with the same `border`); mvs (F, n_blocks, 4, 2) int16, mses (F, n_blocks, 4) int32 as aomhip_tf_motion_search_frames
-    writes them.  Returns the filtered planes (border-extended arrays of the same shapes; only the block-covered area is written)."""
+    writes them.  Returns the filtered planes (border-extended arrays of the same shapes; only the block-covered area is written).
+    stats=True: returns (planes, TfWeightStats) -- what the weights of this very run were (see TfWeightStats)."""
     P, F = len(planes_b), len(planes_b[0])
     e16 = int(planes_b[0][0].dtype != np.uint8)
     origins = (C.c_void_p * (3 * F))()
@@ -180,13 +215,20 @@ def tf_apply_frames(planes_b, border, width, height, filter_frame, mvs, mses, no
     nl = (C.c_double * 3)(*([float(v) for v in noise_levels] + [0.0] * 3)[:3])
     mv = np.ascontiguousarray(mvs, np.int16)
     ms = np.ascontiguousarray(mses, np.int32)
-    f = lib.orc_tf_apply_frames
+    args = (origins, strides, C.c_int(F), C.c_int(filter_frame), C.c_int(width), C.c_int(height), C.c_int(P), C.c_int(ss_x), C.c_int(ss_y), nl,
+            C.c_void_p(mv.ctypes.data), C.c_void_p(ms.ctypes.data), C.c_int(q_factor), C.c_int(filter_strength), out_ptrs, ostr, C.c_int(e16),
+            C.c_int(bd), C.c_int(threads), C.c_int(block_first), C.c_int(block_step))
+    f = lib.orc_tf_apply_frames_stats if stats else lib.orc_tf_apply_frames
     f.restype = None
     f.argtypes = None
-    f(origins, strides, C.c_int(F), C.c_int(filter_frame), C.c_int(width), C.c_int(height), C.c_int(P), C.c_int(ss_x), C.c_int(ss_y), nl,
-      C.c_void_p(mv.ctypes.data), C.c_void_p(ms.ctypes.data), C.c_int(q_factor), C.c_int(filter_strength), out_ptrs, ostr, C.c_int(e16),
-      C.c_int(bd), C.c_int(threads), C.c_int(block_first), C.c_int(block_step))
-    return outs
+    if not stats:
+        f(*args)
+        return outs
+    hist, min_ulp = np.zeros((3, TF_HIST), np.int64), np.zeros(3, np.float64)
+    ties = [np.zeros(outs[p].shape, np.uint8) for p in range(P)]
+    tie_ptrs = (C.c_void_p * 3)(*[_addr(ties[p], border, border) for p in range(P)] + [None] * (3 - P))
+    f(*args, C.c_void_p(hist.ctypes.data), C.c_void_p(min_ulp.ctypes.data), tie_ptrs)
+    return outs, TfWeightStats(hist[:P], min_ulp[:P], [t.astype(bool) for t in ties])
 
 
 def build_compound_pred(ref0_b, ref1_b, border, width, height, w, h, blocks, mv0, mv1, filter_x=0, filter_y=0, fwd=0, bck=0, bd=8, ss_x=0, ss_y=0):
