@@ -5,7 +5,9 @@
 //
 // The reference filters in place and keeps line / column buffers so that every tap reads PRE-CDEF
 // (deblocked) pixels, with CDEF_VERY_LARGE outside the frame.  An out-of-place kernel (read the deblocked
-// plane, write the CDEF plane) has exactly those semantics with no buffers.
+// plane, write the CDEF plane) needs no buffers; that it gives what the reference's frame loop gives
+// (av1_cdef_fb_row with cdef_prepare_fb's line / column buffers, interpreted) is what
+// tests/golden/ref_eval_filter_frame.npz and tests/test_gpu_filter_frame.py check.
 //
 // One workgroup per 64x64 filter block:
 //   1. the 68 x 72 footprint (2-row / 4-column halo) is staged in LDS as uint16 with 8-byte loads, 0x4000 outside

@@ -27,15 +27,20 @@ TXW = [4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64]
 TXH = [4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16]
 
 
-def make_evaluator():
+FILES = ["aom_dsp/txfm_common.h", "aom_dsp/aom_dsp_common.h", "av1/common/common.h", "av1/common/enums.h", "av1/common/common_data.h", "av1/common/common_data.c", "av1/common/seg_common.h",
+         "av1/common/mv.h", "aom_scale/yv12config.h", "av1/common/blockd.h", "av1/common/av1_loopfilter.h", "av1/common/av1_loopfilter.c",
+         "av1/common/cdef_block.h", "av1/common/cdef.c"]
+
+
+def make_evaluator(files=FILES, typedefs=None):
+    """files: what to load (gen_ref_eval_filter_frame.py adds the filters themselves); typedefs: names from headers that are not loaded."""
     ev = evaluator([])
+    ev.typedefs.update(typedefs or {})
     for nm, v in (("AOM_PLANE_Y", "0"), ("AOM_PLANE_U", "1"), ("AOM_PLANE_V", "2")):   # aom/aom_image.h (#defines inside a struct body)
         ev.define(nm, v)
     for nm in ("TX_SIZE", "TX_TYPE", "PREDICTION_MODE", "MV_REFERENCE_FRAME", "BLOCK_SIZE", "PARTITION_TYPE", "PLANE_TYPE", "EDGE_DIR"):
         ev.typedefs.setdefault(nm, R.U8 if nm not in ("MV_REFERENCE_FRAME",) else R.I8)
-    for f in ["aom_dsp/txfm_common.h", "aom_dsp/aom_dsp_common.h", "av1/common/common.h", "av1/common/enums.h", "av1/common/common_data.h", "av1/common/common_data.c", "av1/common/seg_common.h",
-              "av1/common/mv.h", "aom_scale/yv12config.h", "av1/common/blockd.h", "av1/common/av1_loopfilter.h", "av1/common/av1_loopfilter.c",
-              "av1/common/cdef_block.h", "av1/common/cdef.c"]:
+    for f in files:
         ev.load("/root/reference/" + f)
     mbmi = ev.structs["<opaque>MB_MODE_INFO"]
     mbmi.fields = [("bsize", R.U8), ("tx_size", R.U8), ("inter_tx_size", ("arr", R.U8, 16)), ("skip_txfm", R.I8), ("ref_frame", ("arr", R.I8, 2)),

@@ -1453,6 +1453,12 @@ class Interp:
             return None, VOID
         if name == "memset":
             (p, _), (c, _), (n, _) = args
+            if p.t.__class__ is StructType and not p.dims and c == 0 and n == self.sizeof(p.t):
+                # memset(&s, 0, sizeof(s)) of one whole struct object: every scalar 0, every pointer NULL
+                if not 0 <= p.off < len(p.buf):
+                    raise CError("memset out of bounds")
+                self.zero_fill(p)
+                return p, PTR
             if p.t.__class__ is not T:
                 raise CError("memset on non-integer elements")
             cnt, rem = divmod(n, p.t.size)
