@@ -129,6 +129,8 @@ MV_COST_ENTROPY, MV_COST_L1_LOWRES, MV_COST_L1_MIDRES, MV_COST_L1_HDRES, MV_COST
 COMP_AVG, COMP_DIST_WTD, COMP_MASK, COMP_OBMC = 0, 1, 2, 3
 blend_item_dtype = np.dtype([("x", "<i2"), ("y", "<i2"), ("w", "<i2"), ("h", "<i2"), ("mask_offset", "<u2"), ("vertical", "u1"), ("reserved", "u1")])
 rect_dtype = np.dtype([("h_start", "<i4"), ("h_end", "<i4"), ("v_start", "<i4"), ("v_end", "<i4")])
+# aomhip_lr_unit_info (48 bytes): RestorationUnitInfo of one unit for aomhip_loop_restoration_filter_units
+lr_unit_info_dtype = np.dtype([("restoration_type", "<i4"), ("sgr_params_idx", "<i4"), ("xqd", "<i4", (2,)), ("hfilter", "<i2", (8,)), ("vfilter", "<i2", (8,))])
 scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_qn", "subpel_y_qn", "dst_x", "dst_y")])   # aomhip_scaled_block
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
@@ -275,6 +277,8 @@ _protos = {
     "aomhip_selfguided_restoration_batch": (C.c_int, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _i64]),
     "aomhip_apply_selfguided_restoration_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _i, _i64]),
     "aomhip_wiener_convolve_add_src_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i]),
+    "aomhip_loop_restoration_filter_units": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "aomhip_lr_units_in_plane": (C.c_int, [_i, _i, _i, _i, _vp, _i]),
     "aomhip_calc_proj_params_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "aomhip_pixel_proj_error_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp]),
     "aomhip_wedge_sse_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -378,6 +382,19 @@ def find_projection(n, pts, pts_inref, bw, bh, mv, model, mi_row, mi_col):
     assert pts.dtype == np.int32 and pts_inref.dtype == np.int32
     return bool(lib.aomhip_find_projection(n, C.c_void_p(pts.ctypes.data), C.c_void_p(pts_inref.ctypes.data), bw, bh, int(mv[0]), int(mv[1]),
                                            C.c_void_p(model.ctypes.data), mi_row, mi_col))
+
+
+def lr_units_in_plane(plane_w, plane_h, unit_size, ss_y):
+    """The restoration-unit limits of one plane in unit_idx order (foreach_rest_unit_in_tile over the whole-frame tile; host, no GPU) -> rect_dtype array"""
+    cap = 4
+    while True:
+        units = np.zeros(cap, rect_dtype)
+        n = int(lib.aomhip_lr_units_in_plane(plane_w, plane_h, unit_size, ss_y, C.c_void_p(units.ctypes.data), cap))
+        if n >= 0:
+            return units[:n].copy()
+        if cap > (1 << 24):
+            raise ValueError("aomhip_lr_units_in_plane(%d, %d, %d, %d): invalid argument" % (plane_w, plane_h, unit_size, ss_y))
+        cap *= 4
 
 
 class AomHipError(RuntimeError):
@@ -905,6 +922,14 @@ class Context:
         hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
         check(lib.aomhip_wiener_convolve_add_src_batch(self.h, C.byref(dat), dat_frame, C.byref(dst), dst_frame, d_units, hu, n_units, d_filters, max_w, max_h),
               "aomhip_wiener_convolve_add_src_batch")
+
+    def loop_restoration_filter_units(self, deblocked, deblocked_frame, cdef, cdef_frame, dst, dst_frame, plane_w, plane_h, ss_y, d_units, h_units, n_units,
+                                      d_info):
+        """av1_loop_restoration_filter_unit for every unit of a list (rect_dtype, lr_unit_info_dtype records), stripe-exact: the context rows at
+        stripe boundaries come from `deblocked`, everything else from `cdef`."""
+        hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
+        check(lib.aomhip_loop_restoration_filter_units(self.h, C.byref(deblocked), deblocked_frame, C.byref(cdef), cdef_frame, C.byref(dst), dst_frame, plane_w,
+                                                       plane_h, ss_y, d_units, hu, n_units, d_info), "aomhip_loop_restoration_filter_units")
 
     def calc_proj_params_batch(self, src, src_frame, dat, dat_frame, d_units, n_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_H, d_C):
         """av1_calc_proj_params[_high_bd] per restoration unit: H (4 int64) and C (2 int64) each."""

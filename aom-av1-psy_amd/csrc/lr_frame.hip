@@ -1,0 +1,292 @@
+// libaomhip -- the loop-restoration FRAME filter on gfx950: av1_loop_restoration_filter_frame (av1/common/restoration.c:1190-1204) for one plane, i.e.
+// av1_loop_restoration_filter_unit (:1024-1090) for every unit of a list, stripe-exact.
+//
+// The reference cuts a unit into processing stripes of SH = 64 >> ss_y rows, moved up by off = 8 >> ss_y rows: stripe k of the plane covers rows
+// [max(0, k SH - off), min((k + 1) SH - off, plane_h)).  Before it filters a stripe [y0, y1) it overwrites the three rows above and below it in the
+// CDEF-filtered frame with DEBLOCKED rows saved before CDEF ran (get_stripe_boundary_info / setup_processing_stripe_boundary :251-371, the rows of
+// av1_loop_restoration_save_boundary_lines :1403-1566) and restores them afterwards.  Here CDEF runs out of place, so the deblocked plane is still
+// resident and the save / overwrite / restore sequence becomes the choice of a SOURCE ROW per staged row (column x always clamped to
+// [0, plane_w - 1]: extend_lines :1388-1401 and av1_extend_frame :137-195):
+//
+//   rows y0 .. y1 - 1                      cdef[y]                                      the frame buffer
+//   y0 - 3, y0 - 2      y0 > 0             deblocked[y0 - 2]                            :313-323 (AOMMAX(i + 2, 0)), saved at :1530
+//   y0 - 1              y0 > 0             deblocked[y0 - 1]
+//   y0 - 3 .. y0 - 1    y0 == 0            cdef[0]                                      copy_above == 0, av1_extend_frame
+//   y1                  y1 < plane_h       deblocked[y1]                                :333-343, saved at :1534
+//   y1 + 1, y1 + 2      y1 < plane_h       deblocked[min(y1 + 1, plane_h - 1)]          AOMMIN(i, 1); lines_to_save == 1 :1418-1452
+//   y1 .. y1 + 2        y1 == plane_h      cdef[plane_h - 1]                            copy_below == 0
+//
+// so the kernel never reads a border pixel of either ring.  (With the single whole-frame tile of av1_foreach_rest_unit_in_plane the rows
+// save_cdef_boundary_lines keeps are never copied back: copy_above / copy_below are 0 exactly where they would be used.)
+//
+// One 256-lane workgroup per (unit, stripe piece, column tile): a piece is 32 rows of ONE stripe (two pieces per luma stripe, one per 4:2:0
+// chroma stripe; a piece starts an even number of rows below its stripe's first row, which is what the r[0] filter's even / odd row rule
+// counts from, selfguided_restoration_fast_internal :766-823), a column tile 64 pixels.  The piece's (32 + 6) x (64 + 6) footprint is staged in LDS
+// once through the row rule.  RESTORE_SGRPROJ: per radius A[] / B[] of the 34 x 66 positions the piece reads go to LDS, the weighted 3 x 3 sums
+// are folded straight into the projection v = (u << 7) + xq0 (flt0 - u) + xq1 (flt1 - u) held in registers (8 pixels per lane) -- neither flt0 / flt1
+// nor anything else goes through global memory.  RESTORE_WIENER: horizontal pass into LDS (aliasing A[]), vertical pass from there, as
+// wiener_kernel of restoration.hip.  RESTORE_NONE (and any other type value): copy.  The arithmetic is that of restoration.hip's kernels
+// (av1_selfguided_restoration + av1_decode_xq + the projection; av1_[highbd_]wiener_convolve_add_src with get_conv_params_wiener(bd)).
+// LDS: 5320 + 2 x 8976 = 23272 bytes, six workgroups per CU by LDS.
+#include "common.h"
+
+namespace aomhip {
+
+#include "sgr_table.inc"
+__device__ const int kLrSgrParams[16][4] = AOMHIP_SGR_PARAMS;
+__device__ const int32_t kLrXByXplus1[256] = AOMHIP_X_BY_XPLUS1;
+__device__ const int32_t kLrOneByX[25] = AOMHIP_ONE_BY_X;
+
+#ifndef AOMHIP_LR_PW
+#define AOMHIP_LR_PW 64                                        // 64 or 32 (tools/gpu_lr_frame.py measured both)
+#endif
+constexpr int kLrPW = AOMHIP_LR_PW, kLrPH = 32;                // piece: columns x rows
+static_assert(kLrPW == 64 || kLrPW == 32, "a wavefront covers one or two rows of a piece");
+constexpr int kLrFW = kLrPW + 6, kLrFH = kLrPH + 6;            // its footprint
+constexpr int kLrAW = kLrPW + 2, kLrAH = kLrPH + 2;            // positions -1 .. 64 x -1 .. 32 of A[] / B[]
+constexpr int kLrMaxUnit = 384;                                // RESTORATION_UNITSIZE_MAX * 3 / 2: a last unit is < 1.5 unit sizes
+constexpr int kLrPerLane = kLrPW * kLrPH / 256;                // pixels per lane: one column, rows lr_row(tid, 0 .. kLrPerLane - 1)
+
+// Row q of a lane.  All rows of a WAVEFRONT have one parity (the r[0] filter treats even and odd rows differently: no divergence): 64 columns -- a
+// wavefront is a row, rows wave + 4 q; 32 columns -- a wavefront is two rows two apart, rows 8 q + (wave & 1) + 2 * half + 4 * (wave >> 1).
+__device__ __forceinline__ int lr_row(int tid, int q) {
+  if (kLrPW == 64) return (tid >> 6) + 4 * q;
+  return 8 * q + ((tid >> 6) & 1) + 2 * ((tid >> 5) & 1) + 4 * (tid >> 7);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb, int deb_stride, const T *__restrict__ cdef, int cdef_stride,
+                                                        T *__restrict__ dst, int dst_stride, const aomhip_rect *__restrict__ units,
+                                                        const aomhip_lr_unit_info *__restrict__ info, int bd, int plane_w, int plane_h, int ss_y,
+                                                        int tiles_x) {
+  __shared__ uint16_t s_d[kLrFH * kLrFW];
+  __shared__ int32_t s_A[kLrAH * kLrAW], s_B[kLrAH * kLrAW];
+  const int tid = threadIdx.x, ui = blockIdx.x;
+  aomhip_rect u = units[ui];   // clipped to the plane and to the largest unit there is: identity for every list the entry point accepts
+  u.h_start = min(max(u.h_start, 0), plane_w); u.v_start = min(max(u.v_start, 0), plane_h);
+  u.h_end = min(min(u.h_end, plane_w), u.h_start + kLrMaxUnit); u.v_end = min(min(u.v_end, plane_h), u.v_start + kLrMaxUnit);
+  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
+  const int p = blockIdx.y / tiles_x, tx = blockIdx.y - p * tiles_x;
+  const int ox = u.h_start + tx * kLrPW;                         // first column of the tile
+  const int k = (u.v_start + off) / SH + p / pps;                // the stripe
+  const int y0 = max(max(0, k * SH - off), u.v_start), y1 = min(min((k + 1) * SH - off, plane_h), u.v_end);
+  const int py0 = y0 + (p % pps) * kLrPH, py1 = min(py0 + kLrPH, y1);
+  if (ox >= u.h_end || py0 >= py1) return;
+  const int pw = min(kLrPW, u.h_end - ox), ph = py1 - py0;
+  const int type = info[ui].restoration_type;
+
+  const int lx = tid & (kLrPW - 1);
+  if (type != 1 && type != 2) {   // RESTORE_NONE; RESTORE_SWITCHABLE and anything else: copy_tile (:1037-1040)
+#pragma unroll
+    for (int q = 0; q < kLrPerLane; ++q) {
+      const int i = lr_row(tid, q);
+      if (i < ph && lx < pw) dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = cdef[(int64_t)(py0 + i) * cdef_stride + ox + lx];
+    }
+    return;
+  }
+
+  // the footprint: rows py0 - 3 .. py1 + 2 through the row rule, columns ox - 3 .. ox + pw + 2 clamped to the plane
+  // (a fixed trip count, unrolled, loads first and LDS stores after: all of a lane's loads are in flight together; rows below a short piece's
+  // footprint load a valid row nobody reads)
+  constexpr int kStage = (kLrFH * kLrFW + 255) / 256;
+  uint16_t staged[kStage];
+#pragma unroll
+  for (int it = 0; it < kStage; ++it) {
+    const int t = min(tid + it * 256, kLrFH * kLrFW - 1);
+    const int fy = t / kLrFW, fx = t - fy * kLrFW;
+    const int y = py0 - 3 + fy, x = min(max(ox - 3 + fx, 0), plane_w - 1);
+    bool from_deb = false;
+    int ry = y;
+    if (y < y0) {
+      from_deb = y0 > 0;
+      ry = from_deb ? max(y, y0 - 2) : 0;
+    } else if (y >= y1) {
+      from_deb = y1 < plane_h;
+      ry = from_deb ? min(y, y1 + 1) : plane_h - 1;
+    }
+    ry = min(max(ry, 0), plane_h - 1);
+    const T *src = from_deb ? deb + (int64_t)ry * deb_stride : cdef + (int64_t)ry * cdef_stride;
+    staged[it] = (uint16_t)src[x];
+  }
+#pragma unroll
+  for (int it = 0; it < kStage; ++it)
+    if (tid + it * 256 < kLrFH * kLrFW) s_d[tid + it * 256] = staged[it];
+  __syncthreads();
+  const int mx = (1 << bd) - 1;
+
+  if (type == 2) {
+    const int idx = info[ui].sgr_params_idx & 15;
+    const int r0 = kLrSgrParams[idx][0], r1 = kLrSgrParams[idx][1];
+    const int xqd0 = info[ui].xqd[0], xqd1 = info[ui].xqd[1];
+    int xq0, xq1;   // av1_decode_xq (:631-643)
+    if (r0 == 0) { xq0 = 0; xq1 = 128 - xqd1; }
+    else if (r1 == 0) { xq0 = xqd0; xq1 = 0; }
+    else { xq0 = xqd0; xq1 = 128 - xq0 - xqd1; }
+    int32_t acc[kLrPerLane];
+#pragma unroll
+    for (int q = 0; q < kLrPerLane; ++q) acc[q] = ((int32_t)s_d[(lr_row(tid, q) + 3) * kLrFW + lx + 3] << 4) << 7;   // u << SGRPROJ_PRJ_BITS
+    const int sh = bd - 8;
+    for (int pass = 0; pass < 2; ++pass) {
+      const int r = pass ? r1 : r0, sv = kLrSgrParams[idx][2 + pass], xq = pass ? xq1 : xq0;
+      if (r <= 0) continue;   // (uniform)
+      const int n = (2 * r + 1) * (2 * r + 1);
+      const uint32_t one_by_x = (uint32_t)kLrOneByX[n - 1];
+      // A, B at piece positions (i, j) in [-1, ph] x [-1, pw]: s_A[(i + 1) * kLrAW + j + 1]; the r[0] filter reads the odd rows only
+      for (int t = tid; t < kLrAH * kLrAW; t += 256) {
+        const int ai = t / kLrAW, aj = t - ai * kLrAW;
+        if (ai > ph + 1 || aj > pw + 1 || (pass == 0 && (ai & 1))) continue;
+        uint32_t sum = 0, sq = 0;
+        for (int y = -r; y <= r; ++y)
+          for (int x = -r; x <= r; ++x) {
+            const uint32_t v = s_d[(ai + 2 + y) * kLrFW + (aj + 2 + x)];   // footprint row of position i is i + 3 = ai + 2
+            sum += v; sq += v * v;
+          }
+        const uint32_t a = (sq + ((1u << (2 * sh)) >> 1)) >> (2 * sh), b = (sum + ((1u << sh) >> 1)) >> sh;
+        const uint32_t pp = (a * n < b * b) ? 0u : a * n - b * b;
+        const uint32_t z = (pp * (uint32_t)sv + (1u << 19)) >> 20;                       // SGRPROJ_MTABLE_BITS
+        const int32_t A = kLrXByXplus1[z < 255u ? z : 255u];
+        s_A[t] = A;
+        s_B[t] = (int32_t)(((uint32_t)(256 - A) * sum * one_by_x + (1u << 11)) >> 12);   // SGRPROJ_SGR, SGRPROJ_RECIP_BITS
+      }
+      __syncthreads();
+#pragma unroll
+      for (int q = 0; q < kLrPerLane; ++q) {
+        const int i = lr_row(tid, q);   // (its parity is the wavefront's)
+        if (i < ph && lx < pw) {
+          const int c = (i + 1) * kLrAW + (lx + 1);
+          int32_t a, b;
+          int nb;
+          if (pass == 0) {
+            if (!(i & 1)) {
+              nb = 5;
+              a = (s_A[c - kLrAW] + s_A[c + kLrAW]) * 6 + (s_A[c - 1 - kLrAW] + s_A[c - 1 + kLrAW] + s_A[c + 1 - kLrAW] + s_A[c + 1 + kLrAW]) * 5;
+              b = (s_B[c - kLrAW] + s_B[c + kLrAW]) * 6 + (s_B[c - 1 - kLrAW] + s_B[c - 1 + kLrAW] + s_B[c + 1 - kLrAW] + s_B[c + 1 + kLrAW]) * 5;
+            } else {
+              nb = 4;
+              a = s_A[c] * 6 + (s_A[c - 1] + s_A[c + 1]) * 5;
+              b = s_B[c] * 6 + (s_B[c - 1] + s_B[c + 1]) * 5;
+            }
+          } else {
+            nb = 5;
+            a = (s_A[c] + s_A[c - 1] + s_A[c + 1] + s_A[c - kLrAW] + s_A[c + kLrAW]) * 4 +
+                (s_A[c - 1 - kLrAW] + s_A[c - 1 + kLrAW] + s_A[c + 1 - kLrAW] + s_A[c + 1 + kLrAW]) * 3;
+            b = (s_B[c] + s_B[c - 1] + s_B[c + 1] + s_B[c - kLrAW] + s_B[c + kLrAW]) * 4 +
+                (s_B[c - 1 - kLrAW] + s_B[c - 1 + kLrAW] + s_B[c + 1 - kLrAW] + s_B[c + 1 + kLrAW]) * 3;
+          }
+          const int32_t d = s_d[(i + 3) * kLrFW + lx + 3];
+          const int32_t v = a * d + b;
+          const int rs = 8 + nb - 4;   // SGRPROJ_SGR_BITS + nb - SGRPROJ_RST_BITS
+          acc[q] += xq * (((v + ((1 << rs) >> 1)) >> rs) - (d << 4));
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < kLrPerLane; ++q) {
+      const int i = lr_row(tid, q);
+      if (i < ph && lx < pw) {
+        const int wv = (int)(int16_t)((acc[q] + (1 << 10)) >> 11);   // (int16_t)ROUND_POWER_OF_TWO(v, SGRPROJ_PRJ_BITS + SGRPROJ_RST_BITS)
+        dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)min(max(wv, 0), mx);
+      }
+    }
+    return;
+  }
+
+  // RESTORE_WIENER: taps 0 .. 6 (tap 7 of the stored filters is 0, InterpKernel padding)
+  uint16_t *s_tmp = reinterpret_cast<uint16_t *>(s_A);   // (ph + 6) x kLrPW
+  int fh[7], fv[7];
+#pragma unroll
+  for (int q = 0; q < 7; ++q) { fh[q] = info[ui].hfilter[q]; fv[q] = info[ui].vfilter[q]; }
+  const int round_0 = bd == 12 ? 5 : 3, round_1 = 14 - round_0;
+  const int limit = (1 << (bd + 8 - round_0)) - 1;   // WIENER_CLAMP_LIMIT
+  for (int t = tid; t < kLrFH * kLrPW; t += 256) {   // temp row r = footprint row r
+    const int r = t / kLrPW, x = t & (kLrPW - 1);
+    if (r >= ph + 6) break;
+    const uint16_t *s = s_d + r * kLrFW + x;   // footprint column x = source column x - 3
+    int sum = ((int)s[3] << 7) + (1 << (bd + 6));
+#pragma unroll
+    for (int q = 0; q < 7; ++q) sum += (int)s[q] * fh[q];
+    s_tmp[t] = (uint16_t)min(max((sum + ((1 << round_0) >> 1)) >> round_0, 0), limit);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < kLrPerLane; ++q) {
+    const int i = lr_row(tid, q);
+    if (i < ph && lx < pw) {
+      const uint16_t *s = s_tmp + i * kLrPW + lx;   // temp row i = source row i - 3
+      int sum = ((int)s[3 * kLrPW] << 7) - (1 << (bd + round_1 - 1));
+#pragma unroll
+      for (int t = 0; t < 7; ++t) sum += (int)s[t * kLrPW] * fv[t];
+      const int v = (sum + ((1 << round_1) >> 1)) >> round_1;
+      dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)min(max(v, 0), mx);
+    }
+  }
+}
+
+}  // namespace aomhip
+
+using namespace aomhip;
+
+extern "C" int aomhip_loop_restoration_filter_units(aomhip_ctx *ctx, const aomhip_planes *deblocked, int deblocked_frame, const aomhip_planes *cdef,
+                                                    int cdef_frame, const aomhip_planes *dst, int dst_frame, int plane_w, int plane_h, int ss_y,
+                                                    const aomhip_rect *d_units, const aomhip_rect *h_units, int n_units,
+                                                    const aomhip_lr_unit_info *d_info) {
+  const char *who = "aomhip_loop_restoration_filter_units";
+  if (!ctx || !deblocked || !cdef || !dst || !deblocked->base || !cdef->base || !dst->base || n_units < 0 || (n_units > 0 && (!d_units || !d_info)) ||
+      deblocked_frame < 0 || deblocked_frame >= deblocked->n_frames || cdef_frame < 0 || cdef_frame >= cdef->n_frames || dst_frame < 0 ||
+      dst_frame >= dst->n_frames || (ss_y != 0 && ss_y != 1) || plane_w < 1 || plane_h < 1) {
+    set_error("%s: invalid argument", who);
+    return AOMHIP_ERR_INVALID;
+  }
+  const int bd = cdef->bit_depth;
+  if ((bd != 8 && bd != 10 && bd != 12) || deblocked->bit_depth != bd || dst->bit_depth != bd) {
+    set_error("%s: the three rings differ in bit depth (%d / %d / %d; 8, 10 or 12)", who, deblocked->bit_depth, bd, dst->bit_depth);
+    return AOMHIP_ERR_INVALID;
+  }
+  if (deblocked->width != cdef->width || deblocked->height != cdef->height || dst->width != cdef->width || dst->height != cdef->height ||
+      plane_w > cdef->width || plane_h > cdef->height) {
+    set_error("%s: the three rings differ in geometry, or the %d x %d crop area does not fit their %d x %d", who, plane_w, plane_h, cdef->width,
+              cdef->height);
+    return AOMHIP_ERR_INVALID;
+  }
+  if ((dst->base == cdef->base && dst_frame == cdef_frame) || (dst->base == deblocked->base && dst_frame == deblocked_frame)) {
+    set_error("%s: dst is one of the inputs (the filter is out of place)", who);
+    return AOMHIP_ERR_INVALID;
+  }
+  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
+  int max_w = kLrMaxUnit, max_stripes = (kLrMaxUnit + SH - 1) / SH + 1;
+  if (h_units) {
+    max_w = 1; max_stripes = 1;
+    for (int i = 0; i < n_units; ++i) {
+      const aomhip_rect &r = h_units[i];
+      if (r.h_start < 0 || r.v_start < 0 || r.h_end > plane_w || r.v_end > plane_h || r.h_end <= r.h_start || r.v_end <= r.v_start ||
+          r.h_end - r.h_start > kLrMaxUnit || r.v_end - r.v_start > kLrMaxUnit) {
+        set_error("%s: unit %d is empty, outside the %d x %d plane or larger than %d", who, i, plane_w, plane_h, kLrMaxUnit);
+        return AOMHIP_ERR_INVALID;
+      }
+      if ((r.v_end != plane_h && (r.v_end + off) % SH != 0) || (r.v_start != 0 && (r.v_start + off) % SH != 0)) {
+        set_error("%s: unit %d covers rows %d .. %d: a unit starts at row 0 or a stripe boundary k * %d - %d and ends at one or at the plane's bottom", who, i,
+                  r.v_start, r.v_end, SH, off);
+        return AOMHIP_ERR_INVALID;
+      }
+      max_w = max(max_w, r.h_end - r.h_start);
+      max_stripes = max(max_stripes, (r.v_end - 1 + off) / SH - (r.v_start + off) / SH + 1);
+    }
+  }
+  if (n_units == 0) return AOMHIP_OK;
+  const int tiles_x = (max_w + kLrPW - 1) / kLrPW;
+  const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * max_stripes * pps));
+  const int64_t eo = (int64_t)deblocked_frame * deblocked->frame_stride + (int64_t)deblocked->border * deblocked->stride + deblocked->border;
+  const int64_t co = (int64_t)cdef_frame * cdef->frame_stride + (int64_t)cdef->border * cdef->stride + cdef->border;
+  const int64_t qo = (int64_t)dst_frame * dst->frame_stride + (int64_t)dst->border * dst->stride + dst->border;
+  if (bd == 8)
+    hipLaunchKernelGGL(lr_frame_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(deblocked->base) + eo, deblocked->stride,
+                       static_cast<const uint8_t *>(cdef->base) + co, cdef->stride, static_cast<uint8_t *>(dst->base) + qo, dst->stride, d_units, d_info,
+                       8, plane_w, plane_h, ss_y, tiles_x);
+  else
+    hipLaunchKernelGGL(lr_frame_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(deblocked->base) + eo,
+                       deblocked->stride, static_cast<const uint16_t *>(cdef->base) + co, cdef->stride, static_cast<uint16_t *>(dst->base) + qo,
+                       dst->stride, d_units, d_info, bd, plane_w, plane_h, ss_y, tiles_x);
+  AOMHIP_LAUNCH_CHECK();
+  return AOMHIP_OK;
+}

@@ -1507,6 +1507,40 @@ int aomhip_wiener_convolve_add_src_batch(aomhip_ctx *ctx, const aomhip_planes *d
                                          const aomhip_rect *d_units, const aomhip_rect *h_units, int n_units, const int16_t *d_filters,
                                          int max_unit_width, int max_unit_height);
 
+/* The loop-restoration FRAME filter of one plane, stripe-exact: av1_loop_restoration_filter_frame (av1/common/restoration.c:1190-1204; the encoder calls it
+ * at av1/encoder/encoder.c:2266-2336) = av1_loop_restoration_filter_unit (:1024-1090) for every unit of the list, with optimized_lr == 0.  The two calls
+ * above read every context row from the CDEF-filtered plane; the reference does not: it cuts a unit into processing stripes of SH = 64 >> ss_y rows
+ * moved up by off = 8 >> ss_y rows -- stripe k covers rows [max(0, k SH - off), min((k + 1) SH - off, plane_h)) -- and at every stripe boundary inside the
+ * frame the three context rows above and below a stripe are DEBLOCKED, pre-CDEF rows (get_stripe_boundary_info / setup_processing_stripe_boundary :251-371,
+ * saved by av1_loop_restoration_save_boundary_lines :1403-1566: two rows, the outer one repeated; one row when the stripe ends one row above the crop
+ * border, :1418-1452).  try_restoration_unit (av1/encoder/pickrst.c:214-221) goes through the same function, so a ONE-unit list is one search trial and
+ * the whole list of aomhip_lr_units_in_plane is the frame filter.  Call it once per plane; for chroma pass the plane's own dimensions and ss_y.
+ *   deblocked   the plane CDEF read (CDEF runs out of place here, so it is still resident: the reference's save / overwrite / restore of boundary
+ *               rows becomes a choice of source row, and the two av1_loop_restoration_save_boundary_lines calls have no counterpart)
+ *   cdef        the plane CDEF wrote;  dst: the output ring, neither of the two inputs.  The three rings agree in width, height and bit depth.
+ *   plane_w/h   the crop dimensions (av1_whole_frame_rect, :42-53), <= the rings' width / height.  Columns and rows are clamped to them (extend_lines
+ *               :1388-1401, av1_extend_frame :137-195): no border pixel of either input is read, and the borders need not be extended.
+ *   d_info[i]   the unit's RestorationUnitInfo.  restoration_type 0 RESTORE_NONE copies the unit from `cdef` (copy_tile :1037-1040), and so does
+ *               RESTORE_SWITCHABLE (3) or any other value; tap 7 of the Wiener filters is not read (0 in an InterpKernel).
+ * Only pixels inside the listed units are written to `dst`.  No scratch memory, nothing is allocated.  h_units: the same list in host memory for
+ * argument checking, or NULL; with it a unit outside the plane, empty or larger than 384 (1.5 RESTORATION_UNITSIZE_MAX) is refused, and so is one
+ * whose v_start is neither 0 nor a stripe boundary k SH - off, or whose v_end is neither plane_h nor a stripe boundary.  On the device a unit is
+ * clipped to the plane and to 384 x 384.
+ * Out of scope: superres (av1_superres_scaled: the boundary rows are then upscaled, :1429-1441) and optimized_lr == 1 (:345-370). */
+typedef struct {
+  int32_t restoration_type;   /* RestorationType: 0 RESTORE_NONE (copy), 1 RESTORE_WIENER, 2 RESTORE_SGRPROJ */
+  int32_t sgr_params_idx;     /* sgrproj_info.ep, 0..15 */
+  int32_t xqd[2];             /* sgrproj_info.xqd */
+  int16_t hfilter[8], vfilter[8];   /* WienerInfo as stored (centre tap minus 128, tap 7 = 0) */
+} aomhip_lr_unit_info;        /* 48 bytes */
+int aomhip_loop_restoration_filter_units(aomhip_ctx *ctx, const aomhip_planes *deblocked, int deblocked_frame, const aomhip_planes *cdef, int cdef_frame,
+                                         const aomhip_planes *dst, int dst_frame, int plane_w, int plane_h, int ss_y, const aomhip_rect *d_units,
+                                         const aomhip_rect *h_units, int n_units, const aomhip_lr_unit_info *d_info);
+/* Host, no GPU: the limits foreach_rest_unit_in_tile / av1_foreach_rest_unit_in_row hand to the visitor for the whole-frame tile
+ * (restoration.c:1206-1294), in unit_idx order; returns the count (av1_lr_count_units_in_tile, :62-64, per direction), or -1 when cap is too small
+ * or an argument is out of range. */
+int aomhip_lr_units_in_plane(int plane_w, int plane_h, int unit_size, int ss_y, aomhip_rect *units, int cap);
+
 /* The self-guided filter's projection statistics (search_sgrproj -> search_selfguided_restoration, av1/encoder/pickrst.c:
  * av1_calc_proj_params[_high_bd] :470-657 = get_proj_subspace's normal equations, av1_[lowbd|highbd]_pixel_proj_error :226-370 = the error of
  * one (xq0, xq1) that finer_search tries; av1_rtcd_defs.pl:454-463).  Unit i is a rectangle of `src` (the source) and `dat` (the degraded plane);
