@@ -111,6 +111,14 @@ inline PlaneView<T> view_of(const aomhip_planes &p) {
   return v;
 }
 
+// one frame of a ring as a ring of one (the batched searches pair src / ref by frame index)
+inline aomhip_planes one_frame(const aomhip_planes &p, int f) {
+  aomhip_planes v = p;
+  v.base = static_cast<char *>(p.base) + (size_t)f * p.frame_stride * (p.bit_depth == 8 ? 1 : 2);
+  v.n_frames = 1;
+  return v;
+}
+
 // The reference's 22 block sizes (av1/common/enums.h:99-124).
 inline bool valid_block(int w, int h) {
   auto p2 = [](int v) { return v >= 4 && v <= 128 && (v & (v - 1)) == 0; };

@@ -10,18 +10,15 @@
 // NEW_MV_MODE_PENALTY -> the decision (:722-752, :777-794) -> next block, with no launch and no global round trip between the links, and
 // only for the blocks that need it (raw_motion_error above the threshold, best_ref_mv != 0).  A link of the chain is ~45 000 clocks of pure
 // latency (8 dependent search rounds with two memory round trips each, profiles/r04_first_pass.md), so the row's wavefronts SPECULATE
-// along it (below): 7.6 -> 4.9 ms per 4K 10-bit frame; the golden-frame leg runs beside the kernel on a second stream (tf_search.hip): 3.7 ms.
+// along it (below): 7.6 -> 4.9 ms per 4K 10-bit frame; the golden-frame leg runs beside the kernel on a second stream (first_pass.hip): 3.7 ms.
 #include <climits>
 
 #define AOMHIP_FPS_DEVICE_ONLY
 #include "fullpel_search.inc"
+#include "search_chain.h"
 
 namespace aomhip {
 namespace {
-
-constexpr int kMaxFullPel = 1023;          // MAX_FULL_PEL_VAL (mcomp_structs.h:22)
-constexpr int kMvLow = -(1 << 14), kMvUpp = 1 << 14;  // MV_LOW / MV_UPP (entropymv.h:75-76)
-__device__ __forceinline__ int rawpel(int x) { return (x + 3 + (x >= 0)) >> 3; }  // GET_MV_RAWPEL (mv.h:28)
 
 // SPEC wavefronts per row, speculating on the chain.  best_ref_mv of block c + 1 is block c's *best_mv, and over most of a frame that is
 // the SAME vector block after block (camera motion, static background).  So the row's wavefronts search blocks c .. c + width - 1 side by
@@ -57,13 +54,7 @@ __global__ __launch_bounds__(SPEC * 64) void fp_row_kernel(PlaneView<T> src, Pla
     BlockScalars bs = BlockScalars::of(b);
     bs.ref_row = brow; bs.ref_col = bcol;
     bs.start_row = rawpel(brow); bs.start_col = rawpel(bcol);
-    int col_min = rawpel(bcol) - kMaxFullPel + ((bcol & 7) ? 1 : 0), row_min = rawpel(brow) - kMaxFullPel + ((brow & 7) ? 1 : 0);
-    int col_max = rawpel(bcol) + kMaxFullPel, row_max = rawpel(brow) + kMaxFullPel;
-    const int lo = rawpel(kMvLow) + 1, hi = rawpel(kMvUpp) - 1;
-    col_min = max(col_min, lo); row_min = max(row_min, lo);
-    col_max = min(col_max, hi); row_max = min(row_max, hi);
-    bs.col_min = max(bs.col_min, col_min); bs.col_max = min(bs.col_max, col_max);
-    bs.row_min = max(bs.row_min, row_min); bs.row_max = min(bs.row_max, row_max);
+    full_limits(bs, brow, bcol);
     return bs;
   };
   // does block c run the chained search from (brow, bcol), and where does it start (pixel position of the clamped start MV's block)?
@@ -106,15 +97,7 @@ __global__ __launch_bounds__(SPEC * 64) void fp_row_kernel(PlaneView<T> src, Pla
           for (int m = 1; m < 64; m <<= 1) sse += __shfl_xor(sse, m, 64);
           const uint32_t qq = q.bit_depth == 10 ? (uint32_t)((sse + 8) >> 4) : q.bit_depth == 12 ? (uint32_t)((sse + 128) >> 8) : (uint32_t)sse;
           const int mrow = m1r * 8, mcol = m1c * 8;
-          int cost;
-          if (C.type == kCostEntropy) {
-            const int dr = mrow - brow, dc = mcol - bcol;
-            const int64_t bits = (int64_t)C.mvjcost[(dc != 0) | ((dr != 0) << 1)] + C.mvcost0[dr] + C.mvcost1[dc];
-            cost = (int)((bits * C.error_per_bit + (1 << 13)) >> 14);
-          } else {
-            const CostCtx cc{ C.type, brow, bcol };
-            cost = cc.var_cost(mrow, mcol);
-          }
+          const int cost = C.err_cost(mrow, mcol, brow, bcol);
           e1 = (int32_t)(qq + (uint32_t)cost + 32u);
         }
       } else {

@@ -48,7 +48,7 @@ struct BlockScalars {
                          __builtin_amdgcn_readfirstlane((int)b.start_row), __builtin_amdgcn_readfirstlane((int)b.start_col) };
   }
 };
-// shared by the first-pass composite (tf_search.hip) and its row-persistent kernel (fp_row.hip)
+// shared by the first-pass composite (first_pass.hip) and its row-persistent kernel (fp_row.hip)
 const SiteTable *fps_device_sites(int device, int method);   // the per-(device, method) table in device memory; nullptr on failure
 SearchArgs fps_search_args(const aomhip_search_params *p, const int32_t *d_mvjcost, const int32_t *d_mvcost_row, const int32_t *d_mvcost_col,
                            int bit_depth, bool want_cost_list);
@@ -58,7 +58,14 @@ struct FpfLegs {
   const int16_t *cmv; const int32_t *cerr;   // chained leg of this column, per row (the column-at-a-time form only)
   const uint32_t *err0, *raw, *gf0;           // get_prediction_error_bitdepth at 0,0: last frame, last source, golden
 };
-struct FpfCost { int type, error_per_bit; const int32_t *mvjcost, *mvcost0, *mvcost1; };
+struct FpfCost {
+  int type, error_per_bit; const int32_t *mvjcost, *mvcost0, *mvcost1;
+  // mv_err_cost_ (mcomp.c:271-308) of the MV (mrow, mcol) around ref_mv, all in 1/8 pel
+  __device__ __forceinline__ int err_cost(int mrow, int mcol, int ref_row, int ref_col) const {
+    if (type == kCostEntropy) return mv_err_cost_bits(mvjcost, mvcost0, mvcost1, mrow - ref_row, mcol - ref_col, error_per_bit);
+    return CostCtx{ type, ref_row, ref_col }.var_cost(mrow, mcol);
+  }
+};
 struct FpfOut { int16_t *best_mv, *full_mv; int32_t *motion_error, *gf_motion_error, *raw_motion_error; };
 // the chained leg of a whole frame in one launch (fp_row.hip); AOMHIP_ERR_INVALID for block sizes it is not built for
 int launch_fp_rows(aomhip_ctx *ctx, const aomhip_planes *src1, const aomhip_planes *last1, int bw, int bh, const aomhip_search_params *p,

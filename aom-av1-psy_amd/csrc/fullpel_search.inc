@@ -93,7 +93,6 @@ __device__ __forceinline__ uint32_t group8_sad_srclds(const uint32_t *src_lds, c
 }
 
 constexpr int kFpsThreads = 256;  // 4 blocks (wavefronts) per workgroup (the form without a window)
-constexpr int kInvalidMv = -32768;  // INVALID_MV_ROW_COL (av1/common/mv.h:27)
 
 #ifndef AOMHIP_FPS_CELL_WAVES
 #define AOMHIP_FPS_CELL_WAVES 4   // the two-block cells (A/B: profiles/r04_search_cell.md; 5 is 1 - 1.5 % faster but spills 10 - 12 VGPRs in ~70 instantiations: not taken)
@@ -863,7 +862,7 @@ __global__ __launch_bounds__(WAVES * 64, CELL ? AOMHIP_FPS_CELL_WAVES : AOMHIP_F
   const aomhip_search_block b = blocks[in_list ? bi : 0];
   const BlockScalars bs = BlockScalars::of(b);
   // an EMPTY window (row_min > row_max) marks a block the caller wants skipped -- the iterations of av1_joint_motion_search a block has already
-  // left (tf_search.hip): nothing is searched, its outputs stay as they are
+  // left (joint_search.hip): nothing is searched, its outputs stay as they are
   const bool have = in_list && bs.row_min <= bs.row_max;
   if constexpr (!CELL) {
     if (!have) return;

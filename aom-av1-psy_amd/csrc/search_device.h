@@ -19,6 +19,8 @@ template <> struct MLoad<4> { using type = MU32; };
 
 enum { kCostEntropy = 0, kCostL1Low = 1, kCostL1Mid = 2, kCostL1Hd = 3, kCostNone = 4 };  // MV_COST_TYPE (mcomp.h:40-50)
 
+constexpr int kInvalidMv = -32768;  // INVALID_MV_ROW_COL (av1/common/mv.h:27)
+
 __device__ __forceinline__ int iabsm(int v) { return v < 0 ? -v : v; }
 
 struct CostCtx {
@@ -35,6 +37,19 @@ struct CostCtx {
     return (lambda * d) >> 3;
   }
 };
+
+// MV_COST_ENTROPY: mv_cost (mcomp.c:249-258) of the difference (dr, dc) to ref_mv in 1/8 pel, from the caller's cost tables ...
+__device__ __forceinline__ int64_t mv_joint_bits(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
+  return (int64_t)mvjcost[(dc != 0) | ((dr != 0) << 1)] + mvcost0[dr] + mvcost1[dc];
+}
+// ... as mv_err_cost_ weighs it (mcomp.c:271-308): ROUND_POWER_OF_TWO_64(bits * error_per_bit, 14) ...
+__device__ __forceinline__ int mv_err_cost_bits(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc, int error_per_bit) {
+  return (int)((mv_joint_bits(mvjcost, mvcost0, mvcost1, dr, dc) * error_per_bit + (1 << 13)) >> 14);
+}
+// ... and as the rate of a result: av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266), ROUND_POWER_OF_TWO(bits * 108, 7)
+__device__ __forceinline__ int mv_bit_cost(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
+  return (int)((mv_joint_bits(mvjcost, mvcost0, mvcost1, dr, dc) * 108 + 64) >> 7);
+}
 
 #ifndef AOMHIP_SEARCH_ALIGNED_LOADS
 #define AOMHIP_SEARCH_ALIGNED_LOADS 0

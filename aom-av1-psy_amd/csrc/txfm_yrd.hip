@@ -12,6 +12,7 @@
 // and yrd_finish_kernel: the function's tail (header rates, the forced-skip check).  ref_best_rd is INT64_MAX as in the caller this serves, so
 // the early exits never trigger.  Blocks lie wholly inside the frame (mb_to_right_edge / mb_to_bottom_edge >= 0).
 #include "common.h"
+#include "search_chain.h"
 
 namespace aomhip {
 namespace {
@@ -96,14 +97,19 @@ int tx_size_of(int w, int h) {
   return -1;
 }
 
+struct YrdMem {   // the composite's work memory for n blocks of nc coefficients per transform block
+  aomhip_txb *txb; int32_t *coeff, *q, *dq, *cost; uint16_t *eob; int64_t *err; uint8_t *tctx, *ectx, *run; YrdAcc *acc;
+  void carve(WorkCarver &c, size_t n, size_t nc) {
+    c(txb, n); c(coeff, n * nc); c(q, n * nc); c(dq, n * nc); c(eob, n); c(err, 2 * n); c(tctx, 2 * n); c(cost, n); c(ectx, n); c(run, 64 * n); c(acc, n);
+  }
+};
+
 }  // namespace
 
 size_t yrd_workspace_bytes(int n_blocks, int bw, int bh) {
   const int txw = bw > 64 ? 64 : bw, txh = bh > 64 ? 64 : bh;
-  const size_t n = (size_t)n_blocks, nc = (size_t)aomhip_tx_max_eob(tx_size_of(txw, txh));
-  return ((n * sizeof(aomhip_txb) + 255) & ~(size_t)255) + 3 * ((n * nc * 4 + 255) & ~(size_t)255) + ((n * 2 + 255) & ~(size_t)255) + ((n * 16 + 255) & ~(size_t)255) +
-         ((n * 2 + 255) & ~(size_t)255) + ((n * 4 + 255) & ~(size_t)255) + ((n + 255) & ~(size_t)255) + ((n * 64 + 255) & ~(size_t)255) +
-         ((n * sizeof(YrdAcc) + 255) & ~(size_t)255);
+  YrdMem m;
+  return carve_bytes([&](WorkCarver &c) { m.carve(c, (size_t)n_blocks, (size_t)aomhip_tx_max_eob(tx_size_of(txw, txh))); });
 }
 
 // the composite on caller-provided work memory (aomhip_single_motion_search_batch carves it out of its own)
@@ -115,33 +121,25 @@ int estimate_txfm_yrd_ws(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip
   const int nc = aomhip_tx_max_eob(tx_size);
   const int pels = txw * txh, scale = (pels > 256) + (pels > 1024);
   const int shift = (1 - scale) * 2;   // (MAX_TX_SCALE - av1_get_tx_scale(tx_size)) * 2
-  const size_t n = (size_t)n_blocks;
-  auto take = [&](size_t bytes) { char *p = ws; ws += (bytes + 255) & ~(size_t)255; return p; };
-  aomhip_txb *d_txb = reinterpret_cast<aomhip_txb *>(take(n * sizeof(aomhip_txb)));
-  int32_t *d_coeff = reinterpret_cast<int32_t *>(take(n * nc * 4)), *d_q = reinterpret_cast<int32_t *>(take(n * nc * 4)), *d_dq = reinterpret_cast<int32_t *>(take(n * nc * 4));
-  uint16_t *d_eob = reinterpret_cast<uint16_t *>(take(n * 2));
-  int64_t *d_err = reinterpret_cast<int64_t *>(take(n * 16));
-  uint8_t *d_tctx = reinterpret_cast<uint8_t *>(take(n * 2));
-  int32_t *d_cost = reinterpret_cast<int32_t *>(take(n * 4));
-  uint8_t *d_ectx = reinterpret_cast<uint8_t *>(take(n));
-  uint8_t *d_run = reinterpret_cast<uint8_t *>(take(n * 64));
-  YrdAcc *d_acc = reinterpret_cast<YrdAcc *>(take(n * sizeof(YrdAcc)));
+  YrdMem m;
+  WorkCarver c{ ws };
+  m.carve(c, (size_t)n_blocks, (size_t)nc);
   const int cols = bw / txw, rows = bh / txh;
   const dim3 grid((unsigned)((n_blocks + 255) / 256)), block(256);
   const int tx_type = (lossless && bw == 4 && bh == 4) ? 16 : 0;   // lossless 4x4: the Walsh-Hadamard transform (av1_fwd_txfm, hybrid_fwd_txfm.c)
   for (int k = 0; k < cols * rows; ++k) {
-    hipLaunchKernelGGL(yrd_prepare_kernel, grid, block, 0, ctx->stream, d_blocks, n_blocks, k, txw, txh, cols, (int)(cols * rows == 1), nc, d_run, d_acc, d_txb, d_tctx);
+    hipLaunchKernelGGL(yrd_prepare_kernel, grid, block, 0, ctx->stream, d_blocks, n_blocks, k, txw, txh, cols, (int)(cols * rows == 1), nc, m.run, m.acc, m.txb, m.tctx);
     AOMHIP_LAUNCH_CHECK();
-    int rc = aomhip_subtract_xform_quant_ex_batch(ctx, src, pred, frame, tx_size, d_txb, n_blocks, 0, tx_type, qparams, AOMHIP_QUANT_B, d_coeff, d_q, d_dq, d_eob, d_err);
+    int rc = aomhip_subtract_xform_quant_ex_batch(ctx, src, pred, frame, tx_size, m.txb, n_blocks, 0, tx_type, qparams, AOMHIP_QUANT_B, m.coeff, m.q, m.dq, m.eob, m.err);
     if (rc != AOMHIP_OK) return rc;
-    rc = aomhip_cost_coeffs_txb_batch(ctx, d_q, tx_size, d_txb, n_blocks, tx_type, d_eob, d_tctx, d_costs, d_cost);
+    rc = aomhip_cost_coeffs_txb_batch(ctx, m.q, tx_size, m.txb, n_blocks, tx_type, m.eob, m.tctx, d_costs, m.cost);
     if (rc != AOMHIP_OK) return rc;
-    rc = aomhip_txb_entropy_context_batch(ctx, d_q, tx_size, d_txb, n_blocks, tx_type, d_eob, d_ectx);
+    rc = aomhip_txb_entropy_context_batch(ctx, m.q, tx_size, m.txb, n_blocks, tx_type, m.eob, m.ectx);
     if (rc != AOMHIP_OK) return rc;
-    hipLaunchKernelGGL(yrd_accumulate_kernel, grid, block, 0, ctx->stream, n_blocks, k, txw, txh, cols, shift, tx_type_rate, d_eob, d_err, d_cost, d_ectx, d_run, d_acc);
+    hipLaunchKernelGGL(yrd_accumulate_kernel, grid, block, 0, ctx->stream, n_blocks, k, txw, txh, cols, shift, tx_type_rate, m.eob, m.err, m.cost, m.ectx, m.run, m.acc);
     AOMHIP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(yrd_finish_kernel, grid, block, 0, ctx->stream, d_blocks, n_blocks, rdmult, lossless, d_acc, d_stats);
+  hipLaunchKernelGGL(yrd_finish_kernel, grid, block, 0, ctx->stream, d_blocks, n_blocks, rdmult, lossless, m.acc, d_stats);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

@@ -9,6 +9,7 @@
 // block into slot j of a scratch ring), ONE `aomhip_variance_batch` launch over the four slots against the source frame (seen as a four-frame ring of
 // stride 0), and `wr_pick_kernel` (the reference's in-order `thismse < bestmse`, the centre's move, the `best_idx == -1` exit).  No host round trip.
 #include "common.h"
+#include "search_chain.h"
 #include "search_device.h"
 #include "warp_error_table.inc"
 #include "warp_fit.h"
@@ -166,17 +167,12 @@ extern "C" int aomhip_refine_warped_mv_batch(aomhip_ctx *ctx, const aomhip_plane
   if (n_blocks == 0) return AOMHIP_OK;
   AOMHIP_TRY(hipSetDevice(ctx->device));
   const size_t n1 = (size_t)n_blocks;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_st = take(n1 * sizeof(WrState)), o_cand = take(4 * n1 * sizeof(WrCand)), o_wb = take(4 * n1 * sizeof(aomhip_warp_block)),
-               o_vc = take(n1 * sizeof(aomhip_var_cand)), o_var = take(4 * n1 * 4), o_sse = take(4 * n1 * 4);
-  char *w = static_cast<char *>(work(ctx, off));
-  if (!w) return AOMHIP_ERR_NOMEM;
-  WrState *st = reinterpret_cast<WrState *>(w + o_st);
-  WrCand *cand = reinterpret_cast<WrCand *>(w + o_cand);
-  aomhip_warp_block *wb = reinterpret_cast<aomhip_warp_block *>(w + o_wb);
-  aomhip_var_cand *vc = reinterpret_cast<aomhip_var_cand *>(w + o_vc);
-  uint32_t *var = reinterpret_cast<uint32_t *>(w + o_var), *sse = reinterpret_cast<uint32_t *>(w + o_sse);
+  WrState *st;
+  WrCand *cand;
+  aomhip_warp_block *wb;
+  aomhip_var_cand *vc;
+  uint32_t *var, *sse;
+  if (!carve_work(ctx, [&](WorkCarver &c) { c(st, n1); c(cand, 4 * n1); c(wb, 4 * n1); c(vc, n1); c(var, 4 * n1); c(sse, 4 * n1); })) return AOMHIP_ERR_NOMEM;
   // the source frame as a four-frame ring of stride 0: slot j of the predictor ring is measured against the same source picture
   aomhip_planes src4 = *src;
   src4.base = static_cast<char *>(src->base) + (int64_t)frame * src->frame_stride * (src->bit_depth == 8 ? 1 : 2);

@@ -1,4 +1,4 @@
-"""aomhip_first_pass_motion_search_batch (csrc/tf_search.hip): NSTEP on the first-pass site table + av1_get_mvpred_sse + the new-MV penalty for
+"""aomhip_first_pass_motion_search_batch (csrc/first_pass.hip): NSTEP on the first-pass site table + av1_get_mvpred_sse + the new-MV penalty for
 a list of blocks, against the interpreted-reference vectors (tests/golden/ref_eval_fp.npz) and against the oracle on whole-frame lists (the
 two zero-MV legs of a first-pass frame) with entropy and L1 MV costs, 8 and 10 bit."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""aomhip_first_pass_inter_frame (csrc/tf_search.hip): the inter half of a first-pass frame in one call, the best_ref_mv chain along each
+"""aomhip_first_pass_inter_frame (csrc/first_pass.hip): the inter half of a first-pass frame in one call, the best_ref_mv chain along each
 block row kept on the device, against the oracle's scalar raster walk of firstpass_inter_prediction (av1/encoder/firstpass.c:690-815)."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""aomhip_motion_estimation_batch (csrc/tf_search.hip): tpl_model.c's motion_estimation (av1/encoder/tpl_model.c:248-301) for a block list --
+"""aomhip_motion_estimation_batch (csrc/motion_search.hip): tpl_model.c's motion_estimation (av1/encoder/tpl_model.c:248-301) for a block list --
 av1_full_pixel_search around a centre MV, then the sub-pel search, with both limit sets derived on the device -- against the oracle's
 composition (whose limit derivations are pinned by the interpreted reference, tests/test_oracle_me.py)."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""aomhip_simple_motion_search_batch (csrc/tf_search.hip): av1_simple_motion_search / av1_simple_motion_sse_var
+"""aomhip_simple_motion_search_batch (csrc/motion_search.hip): av1_simple_motion_search / av1_simple_motion_sse_var
 (av1/encoder/motion_search_facade.c:925-1060) for one level of the partition tree of every superblock -- full-pel search from the
 parent's start MV around ref_mv = 0, the sub-pel search, the EIGHTTAP_REGULAR predictor and vf(src, pred) -- against the oracle's
 composition of the pieces the interpreted reference pins (full-pel search, sub-pel trees, limits, convolve, variance)."""

@@ -1,5 +1,5 @@
 """aomhip_subpel_tree_list_batch against the interpreted reference (tests/golden/ref_eval_single.npz: the sub-pel trees on a
-last_mv_search_list, where they stop and what they leave) and aomhip_single_motion_search_batch (csrc/tf_search.hip: two start candidates,
+last_mv_search_list, where they stop and what they leave) and aomhip_single_motion_search_batch (csrc/motion_search.hip: two start candidates,
 second-MV refinement, rate) against the oracle's composition of av1_single_motion_search's SIMPLE_TRANSLATION core."""
 import ctypes as C
 

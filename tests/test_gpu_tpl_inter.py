@@ -1,4 +1,4 @@
-"""aomhip_tpl_inter_estimation_batch (csrc/tf_search.hip): the inter leg of tpl_model.c's mode_estimation (av1/encoder/tpl_model.c:620-770) for
+"""aomhip_tpl_inter_estimation_batch (csrc/tpl_inter.hip): the inter leg of tpl_model.c's mode_estimation (av1/encoder/tpl_model.c:620-770) for
 independent blocks -- candidate pruning by SAD, motion_estimation from every remaining candidate, the EIGHTTAP_REGULAR predictor, the DCT SATD cost,
 the best reference -- against the oracle's composition of the pinned pieces."""
 import numpy as np
