@@ -62,7 +62,9 @@ def header_protos():
     return out
 
 
-def test_exact_signature_entry_points_match_add_proto():
+def checked_entry_points():
+    """-> (checked, bad): the reference names of every header entry point aomhip_<stem> that has an add_proto (aom_<stem>, av1_<stem> or
+    <stem>), and those of them whose signature differs.  tests/test_gpu_refc_rtcd.py drives exactly this list against the compiled reference."""
     ref, hdr = reference_protos(), header_protos()
     assert len(ref) > 1000 and len(hdr) > 200, (len(ref), len(hdr))
     checked, bad = [], []
@@ -74,6 +76,11 @@ def test_exact_signature_entry_points_match_add_proto():
                 if ref[cand] != sig:
                     bad.append((cand, "reference", ref[cand], "aomhip.h", sig))
                 break
+    return checked, bad
+
+
+def test_exact_signature_entry_points_match_add_proto():
+    checked, bad = checked_entry_points()
     assert not bad, bad
     fams = {"quantize": 12, "lpf": 40, "fwd_txfm2d": 19, "inv_txfm2d_add": 19, "cdef": 10, "subtract": 2, "sad": 2, "variance": 1}
     for key, n in fams.items():
