@@ -131,6 +131,8 @@ blend_item_dtype = np.dtype([("x", "<i2"), ("y", "<i2"), ("w", "<i2"), ("h", "<i
 rect_dtype = np.dtype([("h_start", "<i4"), ("h_end", "<i4"), ("v_start", "<i4"), ("v_end", "<i4")])
 # aomhip_lr_unit_info (48 bytes): RestorationUnitInfo of one unit for aomhip_loop_restoration_filter_units
 lr_unit_info_dtype = np.dtype([("restoration_type", "<i4"), ("sgr_params_idx", "<i4"), ("xqd", "<i4", (2,)), ("hfilter", "<i2", (8,)), ("vfilter", "<i2", (8,))])
+# aomhip_sgr_search_result (24 bytes): one record of aomhip_search_selfguided_restoration_batch
+sgr_search_result_dtype = np.dtype([("ep", "<i4"), ("xqd", "<i4", (2,)), ("visited", "<i4"), ("err", "<i8")])
 scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_qn", "subpel_y_qn", "dst_x", "dst_y")])   # aomhip_scaled_block
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
@@ -281,6 +283,7 @@ _protos = {
     "aomhip_lr_units_in_plane": (C.c_int, [_i, _i, _i, _i, _vp, _i]),
     "aomhip_calc_proj_params_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "aomhip_pixel_proj_error_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp]),
+    "aomhip_search_selfguided_restoration_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_wedge_sse_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "aomhip_wedge_sign_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "aomhip_wedge_compute_delta_squares_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
@@ -940,6 +943,13 @@ class Context:
         """av1_[lowbd|highbd]_pixel_proj_error per (unit, xq): int64 each."""
         check(lib.aomhip_pixel_proj_error_batch(self.h, C.byref(src), src_frame, C.byref(dat), dat_frame, d_units, n_units, d_flt0, d_flt1, flt_stride, flt_pitch,
                                                 d_radii, d_xq, n_xq, d_err), "aomhip_pixel_proj_error_batch")
+
+    def search_selfguided_restoration_batch(self, src, src_frame, dat, dat_frame, d_units, h_units, n_units, enable_sgr_ep_pruning, d_best, d_per_ep=None):
+        """search_selfguided_restoration per restoration unit (rect_dtype records): d_best[i] = the unit's SgrprojInfo and its error, d_per_ep[16 i + ep]
+        = what compute_sgrproj_err gave for that parameter set (sgr_search_result_dtype records; d_per_ep may be None)."""
+        hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
+        check(lib.aomhip_search_selfguided_restoration_batch(self.h, C.byref(src), src_frame, C.byref(dat), dat_frame, d_units, hu, n_units, enable_sgr_ep_pruning,
+                                                             d_best, d_per_ep), "aomhip_search_selfguided_restoration_batch")
 
     def scaled_pred_batch(self, ref, ref_frame, pred, pred_frame, bw, bh, fx, fy, x_step_qn, y_step_qn, d_blocks, n_blocks):
         """av1_[highbd_]convolve_2d_scale for a batch of blocks (scaled_block_dtype records), single reference."""

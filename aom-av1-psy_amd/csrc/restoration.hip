@@ -18,6 +18,7 @@
 // The 8-bit function's down-sampled mode (every 4th row weighted by 4, the last one by what is left,
 // pickrst.c:988-1013) is a per-row weight here.
 #include "common.h"
+#include "restoration_device.h"
 
 namespace aomhip {
 
@@ -179,15 +180,6 @@ __device__ const int32_t kXByXplus1[256] = AOMHIP_X_BY_XPLUS1;
 __device__ const int32_t kOneByX[25] = AOMHIP_ONE_BY_X;
 
 constexpr int kSgrTile = 32, kSgrFoot = kSgrTile + 6, kSgrAB = kSgrTile + 2;
-
-// A unit as the kernels use it: clipped to the plane and to the stated maximum size.  Identity for every unit the entry points accept -- they can
-// only check the optional HOST copy of the list -- and what keeps a bad device-side rectangle from writing past the caller's flt0 / flt1 rows or
-// outside the destination plane (it then filters the clipped rectangle).
-__device__ __forceinline__ aomhip_rect clip_unit(aomhip_rect u, int plane_w, int plane_h, int max_w, int max_h) {
-  u.h_start = min(max(u.h_start, 0), plane_w); u.v_start = min(max(u.v_start, 0), plane_h);
-  u.h_end = min(min(u.h_end, plane_w), u.h_start + max_w); u.v_end = min(min(u.v_end, plane_h), u.v_start + max_h);
-  return u;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void selfguided_kernel(const T *__restrict__ dgd, int dgd_stride, const aomhip_rect *__restrict__ units,
@@ -416,6 +408,19 @@ __global__ __launch_bounds__(256) void proj_error_kernel(const T *__restrict__ s
   if (threadIdx.x == 0) err_out[(int64_t)ui * n_xq + qi] = err;
 }
 
+void launch_selfguided(aomhip_ctx *ctx, const aomhip_planes *dgd, int dgd_frame, const aomhip_rect *d_units, int n_units, const int32_t *d_sgr_params_idx,
+                       int max_unit_width, int max_unit_height, int32_t *d_flt0, int32_t *d_flt1, int flt_stride, int64_t flt_pitch) {
+  const int tiles_x = (max_unit_width + kSgrTile - 1) / kSgrTile, tiles_y = (max_unit_height + kSgrTile - 1) / kSgrTile;
+  const int64_t po = (int64_t)dgd_frame * dgd->frame_stride + (int64_t)dgd->border * dgd->stride + dgd->border;
+  const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * tiles_y));
+  if (dgd->bit_depth == 8)
+    hipLaunchKernelGGL(selfguided_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(dgd->base) + po, dgd->stride, d_units,
+                       d_sgr_params_idx, 8, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
+  else
+    hipLaunchKernelGGL(selfguided_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(dgd->base) + po, dgd->stride, d_units,
+                       d_sgr_params_idx, dgd->bit_depth, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
+}
+
 }  // namespace aomhip
 
 using namespace aomhip;
@@ -519,15 +524,7 @@ extern "C" int aomhip_selfguided_restoration_batch(aomhip_ctx *ctx, const aomhip
     }
   }
   if (n_units == 0) return AOMHIP_OK;
-  const int tiles_x = (max_unit_width + kSgrTile - 1) / kSgrTile, tiles_y = (max_unit_height + kSgrTile - 1) / kSgrTile;
-  const int64_t po = (int64_t)dgd_frame * dgd->frame_stride + (int64_t)dgd->border * dgd->stride + dgd->border;
-  const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * tiles_y));
-  if (dgd->bit_depth == 8)
-    hipLaunchKernelGGL(selfguided_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(dgd->base) + po, dgd->stride, d_units,
-                       d_sgr_params_idx, 8, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
-  else
-    hipLaunchKernelGGL(selfguided_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(dgd->base) + po, dgd->stride, d_units,
-                       d_sgr_params_idx, dgd->bit_depth, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
+  launch_selfguided(ctx, dgd, dgd_frame, d_units, n_units, d_sgr_params_idx, max_unit_width, max_unit_height, d_flt0, d_flt1, flt_stride, flt_pitch);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

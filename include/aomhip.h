@@ -1555,6 +1555,28 @@ int aomhip_pixel_proj_error_batch(aomhip_ctx *ctx, const aomhip_planes *src, int
                                   const aomhip_rect *d_units, int n_units, const int32_t *d_flt0, const int32_t *d_flt1, int flt_stride, int64_t flt_pitch,
                                   const int32_t *d_radii, const int32_t *d_xq, int n_xq, int64_t *d_err);
 
+/* search_selfguided_restoration (av1/encoder/pickrst.c:804-863, search_sgrproj's call at :916-920) for every restoration unit of a list, on the device
+ * from the filter to the winner: per unit and parameter set compute_sgrproj_err (:774-791: apply_sgr, get_proj_subspace's 2 x 2 solve with its overflow
+ * branch, encode_xq, finer_search_pixel_proj_error's walk as written), get_best_error (strict <: the first set wins a tie) over all 16 sets or, with
+ * enable_sgr_ep_pruning (lpf_sf), the 4 seeds, the winner's neighbours inside group 1 and one set each of groups 2 and 3 (:44-53, :826-856).
+ * `src` = the source ring, `dat` = the degraded (deblocked + CDEF) ring of the same geometry and bit depth (8, 10 or 12), border >= 3 and extended like
+ * av1_extend_frame leaves it (aomhip_selfguided_restoration_batch's contract).  Units up to 384 x 384, luma or chroma planes; a unit's result does
+ * not depend on the processing-unit cut (tests/test_golden_sgr.py), so there is no pu_width / pu_height.
+ *   d_best[i]            ep, xqd = the SgrprojInfo the function returns; err = besterr; visited = the number of parameter sets evaluated
+ *   d_per_ep[16 i + ep]  exqd and err of compute_sgrproj_err for that set, visited = 1; a set the pruned search did not reach has visited = 0,
+ *                        err = -1, xqd = { 0, 0 }.  May be NULL.
+ * Stream-ordered on the context's stream, no host synchronisation (the filter outputs live in the context's work memory, at most 512 MiB of them at
+ * a time; growing it synchronises, so run the call once before capturing it).  h_units: the same list in host memory for argument checking and for
+ * sizing the scratch rows to the largest unit, or NULL (384 x 384 is then assumed; on the device a unit is clipped to the plane and to that size).
+ * count_sgrproj_bits, the RD comparison and skip_sgr_eval read encoder state and stay with the host. */
+typedef struct {
+  int32_t ep, xqd[2], visited;
+  int64_t err;
+} aomhip_sgr_search_result;   /* 24 bytes */
+int aomhip_search_selfguided_restoration_batch(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dat, int dat_frame,
+                                               const aomhip_rect *d_units, const aomhip_rect *h_units, int n_units, int enable_sgr_ep_pruning,
+                                               aomhip_sgr_search_result *d_best, aomhip_sgr_search_result *d_per_ep);
+
 /* ------------------------------------------------------------------ rtcd-signature conformance entry points */
 
 /* aom_dsp_rtcd_defs.pl:762-763 aom_sad{W}x{H} / aom_sad_skip_{W}x{H}; host pointers. */
