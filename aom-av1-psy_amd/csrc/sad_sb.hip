@@ -6,9 +6,15 @@
 // Structure (round 2; the round-1 form staged one (sb_w + 2 range) x (sb_h + 2 range) window per cell and so
 // pulled every reference byte through L2 -> LDS 2.7 times and through the fabric 1.4-1.9 times):
 //   * A persistent workgroup owns one STRIP -- a column of cells of one frame -- and walks it top to bottom.
-//     The reference window lives in an LDS ring of R = 2 sb_h + 2 range rows indexed by (y - ymin) mod R, so
-//     going from one cell to the next brings in only the sb_h NEW rows: every reference byte of the strip
-//     crosses L2 -> LDS once; what is left of the halo is the 2 range columns shared with the neighbour strips.
+//     The reference window lives in an LDS ring of R = 2 sb_h + 2 range rows, a FIFO from the strip's first row
+//     (row y in slot (y - y_first) mod R), so going from one cell to the next brings in only the sb_h NEW rows:
+//     every reference byte of the strip crosses L2 -> LDS once; what is left of the halo is the 2 range columns
+//     shared with the neighbour strips.
+//   * A strip is a stream of POSITIONS.  Its first window comes in as ordinary batches (as many rows as a loader
+//     group's registers hold, at least sb_h) through the loaders' pipeline -- fill positions in front of cell 0, where the evaluating wavefronts only meet the
+//     barrier -- and batch 0, the last of them, brings source cell 0 and its list slices like any later batch.
+//     (Until profiles/sad_strip_stream.md a prologue run by all 1024 lanes copied the first window: general
+//     per-chunk address arithmetic, the full load latency with nothing behind it, ~10 500 clock ticks per strip.)
 //   * Wave specialisation: 8 EVALUATING wavefronts + 8 LOADER wavefronts per workgroup.  The loaders bring in
 //     everything a step needs -- the new ring rows, the step's SOURCE cell (double buffered) and its slice of the
 //     two work lists -- through registers: the loads for step cy + 2 are in flight (in the loaders' VGPRs, so
@@ -128,7 +134,7 @@ struct StripArgs {
   int ring_off, src_off[2], gdesc_off[2], cdesc_off[2], misc_off, seg_off;  // LDS byte offsets
   int gcap, ccap;              // list entries per descriptor buffer
   int shift;
-  int dbg;  // AOMHIP_SB_DBG (timing ablations only, results invalid): 1 = no evaluation, 2 = no steady-state DMA
+  int dbg;  // AOMHIP_SB_DBG (timing ablations only, results invalid): 1 = no evaluation, 2 = no steady-state DMA, 256 = fill positions only
 };
 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -137,7 +143,7 @@ __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlan
 #define AOMHIP_SB_DBG_KNOBS 0
 #endif
 #ifdef AOMHIP_SB_PROF  // phase timing of wave 0 of every workgroup (tools/gpu_sb_prof.sh builds a library with it)
-__device__ unsigned long long g_sb_prof[32];  // [0..7] first evaluating wavefront, [8..15] first loader wavefront, [16..31] barrier wait of wavefront w
+__device__ unsigned long long g_sb_prof[32];  // [0..7] first evaluating wavefront ([5] = its fill positions), [8..15] first loader wavefront, [16..31] barrier wait of wavefront w
 #define SB_T(v) const long long v = (long long)__builtin_readcyclecounter()
 #define SB_ACC(i, t1, t0) prof_acc[i] += (unsigned long long)((t1) - (t0))
 #define SB_DECL unsigned long long prof_acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, prof_wait = 0
@@ -167,9 +173,6 @@ template <int EVAL, int UPL_, int LOADERS, int RING_N, int SRC_N, int G_N, int C
 };
 // 8 evaluating wavefronts with two row units per lane + 8 loader wavefronts.
 using CfgWide = Cfg<512, 2, 8, 6, 4, 2, 1>;
-// 12 evaluating wavefronts with ONE row unit per lane + 4 loader wavefronts that keep twice the chunks in flight each (experiment,
-// see use_deep()).
-using CfgDeep = Cfg<768, 1, 4, 9, 6, 4, 2>;
 template <typename T, int W, int H, bool SKIP, typename C, bool VAR = false>
 __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, PlaneView<T> ref, StripArgs a,
                                                                   const aomhip_sad_x4d_cand *__restrict__ groups,
@@ -246,9 +249,11 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
   // the loaders keep the memory system saturated (ISA of the first version: three s_load_dword + s_waitcnt at the top of every step).
   const int src_off0 = a.src_off[0], src_off1 = a.src_off[1], gdesc_off0 = a.gdesc_off[0], gdesc_off1 = a.gdesc_off[1];
   const int cdesc_off0 = a.cdesc_off[0], cdesc_off1 = a.cdesc_off[1];
-  auto src_off_of = [&](int buf) { return buf ? src_off1 : src_off0; };
-  auto gdesc_off_of = [&](int buf) { return buf ? gdesc_off1 : gdesc_off0; };
-  auto cdesc_off_of = [&](int buf) { return buf ? cdesc_off1 : cdesc_off0; };
+  // (Arithmetic on both values, buf = 0 / 1, not `buf ? off1 : off0`: the two loads of a conditional's arms get sunk into ONE load through a
+  // select of two addresses, and where that survives inlining the offsets live in scratch and every use in a step is a flat load.)
+  auto src_off_of = [&](int buf) { return src_off0 + buf * (src_off1 - src_off0); };
+  auto gdesc_off_of = [&](int buf) { return gdesc_off0 + buf * (gdesc_off1 - gdesc_off0); };
+  auto cdesc_off_of = [&](int buf) { return cdesc_off0 + buf * (cdesc_off1 - cdesc_off0); };
 
   // The two roles run two separate instantiations of everything below: values only one role needs (the evaluation's
   // unit tables, the loaders' staging registers and chunk offsets) then never share a live range with the other role's
@@ -329,63 +334,36 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
       const uint32_t *gwords = groups ? reinterpret_cast<const uint32_t *>(glist) : reinterpret_cast<const uint32_t *>(ref_frame);
       const uint32_t *cwords = cands ? reinterpret_cast<const uint32_t *>(clist) : reinterpret_cast<const uint32_t *>(ref_frame);
       const int gwords_n = groups ? n_groups * 5 : 1, cwords_n = cands ? n_cands * 2 : 1;
-      auto request_gen = [&](const Batch &b, Stage &st, int me, int n) {
-        const int total_r = (b.yb - b.ya) * a.cpr, total_s = b.ns * a.scpr;
-        const char *rb = ref_frame + (int64_t)b.ya * gpitch + (int64_t)wx0 * kES;
-        const char *sb_ = src_frame + (int64_t)b.sy0 * sgpitch + (int64_t)sx0 * kES;
-  #pragma unroll
-        for (int i = 0; i < kRingN; ++i) {
-          const unsigned q = (unsigned)max(min(me + i * n, total_r - 1), 0);
-          const unsigned row = __umulhi(q, a.magic_cpr), col = q - row * (unsigned)a.cpr;
-          st.ring[i] = *reinterpret_cast<const V4 *>(rb + (row * (unsigned)gpitch + (unsigned)min((int)col, colmax) * 16u));
-        }
-  #pragma unroll
-        for (int i = 0; i < kSrcN; ++i) {
-          const unsigned q = (unsigned)max(min(me + i * n, total_s - 1), 0);
-          const unsigned row = __umulhi(q, a.magic_scpr), col = q - row * (unsigned)a.scpr;
-          st.srcv[i] = *reinterpret_cast<const V4 *>(sb_ + (row * (unsigned)sgpitch + (unsigned)min((int)col, scolmax) * 16u));
-        }
+      // The further slices of a crowded bucket (overflow() below) carry list words only.
+      struct Words { uint32_t g[kGN]; uint32_t c[kCN]; };
+      auto request_lists = [&](const Batch &b, Words &st, int me, int n) {
   #pragma unroll
         for (int i = 0; i < kGN; ++i) st.g[i] = gwords[(unsigned)max(min(b.g0 * 5 + min(me + i * n, b.ng * 5 - 1), gwords_n - 1), 0)];
   #pragma unroll
         for (int i = 0; i < kCN; ++i) st.c[i] = cwords[(unsigned)max(min(b.c0 * 2 + min(me + i * n, b.nc * 2 - 1), cwords_n - 1), 0)];
       };
-      auto commit_gen = [&](const Batch &b, const Stage &st, int me, int n) {
-        const int total_r = (b.yb - b.ya) * a.cpr, total_s = b.ns * a.scpr;
-        const unsigned s_first = (unsigned)((b.ya - a.ymin) % a.R);
-  #pragma unroll
-        for (int i = 0; i < kRingN; ++i) {
-          const unsigned q = (unsigned)(me + i * n);
-          if ((int)q < total_r) {
-            const unsigned row = __umulhi(q, a.magic_cpr), col = q - row * (unsigned)a.cpr;
-            unsigned sl = s_first + row;
-            sl = min(sl, sl - (unsigned)a.R);
-            const V4 v = st.ring[i];
-            *reinterpret_cast<V4 *>(lds + a.ring_off + sl * a.pitch + col * 16) = v;
-            if (kMirror > 0 && sl < (unsigned)kMirror)
-              *reinterpret_cast<V4 *>(lds + a.ring_off + (sl + a.R) * a.pitch + col * 16) = v;
-          }
-        }
-  #pragma unroll
-        for (int i = 0; i < kSrcN; ++i) {
-          const unsigned q = (unsigned)(me + i * n);
-          if ((int)q < total_s) {
-            const unsigned row = __umulhi(q, a.magic_scpr), col = q - row * (unsigned)a.scpr;
-            *reinterpret_cast<V4 *>(lds + src_off_of(b.buf) + row * a.spitch + col * 16) = st.srcv[i];
-          }
-        }
+      auto commit_lists = [&](const Batch &b, const Words &st, int me, int n) {
+        const int goff = gdesc_off_of(b.buf), coff = cdesc_off_of(b.buf);
   #pragma unroll
         for (int i = 0; i < kGN; ++i)
-          if (me + i * n < b.ng * 5) *reinterpret_cast<uint32_t *>(lds + gdesc_off_of(b.buf) + (me + i * n) * 4) = st.g[i];
+          if (me + i * n < b.ng * 5) *reinterpret_cast<uint32_t *>(lds + goff + (me + i * n) * 4) = st.g[i];
   #pragma unroll
         for (int i = 0; i < kCN; ++i)
-          if (me + i * n < b.nc * 2) *reinterpret_cast<uint32_t *>(lds + cdesc_off_of(b.buf) + (me + i * n) * 4) = st.c[i];
+          if (me + i * n < b.nc * 2) *reinterpret_cast<uint32_t *>(lds + coff + (me + i * n) * 4) = st.c[i];
       };
       auto win_y0 = [&](int cy) { return max(cy * a.sb_h - a.range, a.ymin); };
       auto win_y1 = [&](int cy) { return min(cy * a.sb_h + a.sb_h + a.range, a.ymax); };
+      // The item as a stream of positions -(n_fill + 1) .. cell_rows - 1.  The first window (rows [y_first, win_y1(0)), up to sb_h + 2 range of
+      // them) arrives as n_fill + 1 ordinary batches of at most fill_h rows each -- what a loader group's staging registers hold, at least
+      // sb_h (the host checks that): FILL batches -n_fill .. -1 carry fill_h ring rows and nothing else, batch 0 the rest of the window (at
+      // least one row) with source cell 0 and its list slices, like any later batch.  The ring is a FIFO from the item's first row: row y
+      // lives in slot (y - y_first) mod R, so fill batch k starts at row (k + n_fill) fill_h of the ring.
+      const int y_first = win_y0(0);
+      const int fill_h = (kRingN * kLT) / a.cpr;
+      const int n_fill = (win_y1(0) - y_first + fill_h - 1) / fill_h - 1;
       struct Seg { int g0, g1, c0, c1; };
-      // The strip's bucket bounds come out of LDS (filled in the prologue): a scalar load from global memory at the top of
-      // a step took 1000-3000 cycles while the loaders keep the memory system saturated.
+      // The strip's bucket bounds come out of LDS (filled once per item by set_up_records() below): a scalar load from global memory
+      // at the top of a step took 1000-3000 cycles while the loaders keep the memory system saturated.
       const int4 *segs = reinterpret_cast<const int4 *>(lds + a.seg_off);
       int4 *wins = reinterpret_cast<int4 *>(lds + a.seg_off) + a.cell_rows, *bats = wins + a.cell_rows;
       auto seg_of = [&](int cy) {
@@ -741,16 +719,18 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
         }
       };
 
-      auto batch_of = [&](int cy) {  // what step cy adds on top of step cy - 1 (nothing past the last cell)
-        const bool real = cy < a.cell_rows;
-        const int cyc = real ? cy : a.cell_rows - 1;  // (addresses of an empty batch stay inside the planes)
+      auto batch_of = [&](int cy) {  // what position cy adds on top of position cy - 1 (cy < 0: a fill batch; nothing past the last cell)
+        const bool fill = cy < 0;
+        const bool real = !fill && cy < a.cell_rows;
+        const int cyc = fill ? 0 : real ? cy : a.cell_rows - 1;  // (addresses of an empty batch stay inside the planes)
         const Seg sg = seg_of(cyc);
         const int4 bv = bats[cyc];  // {first new row, new rows, source cell rows, ring byte offset of the first new row}
+        const int frow = (cy + n_fill) * fill_h;  // a fill batch: its first row, counted from the item's first row (= its ring slot)
         Batch b;
-        b.ya = uni(bv.x);
-        b.yb = real ? b.ya + uni(bv.y) : b.ya;
+        b.ya = fill ? y_first + frow : uni(bv.x);
+        b.yb = fill ? b.ya + fill_h : real ? b.ya + uni(bv.y) : b.ya;
         b.sy0 = cyc * a.sb_h; b.ns = real ? uni(bv.z) : 0;
-        b.first = (unsigned)uni(bv.w);
+        b.first = fill ? (unsigned)(frow * a.pitch) : (unsigned)uni(bv.w);
         b.g0 = sg.g0; b.ng = real ? min(sg.g1 - sg.g0, a.gcap) : 0;
         b.c0 = sg.c0; b.nc = real ? min(sg.c1 - sg.c0, a.ccap) : 0;
         b.buf = cy & 1;
@@ -760,8 +740,10 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
       };
       // Per-step records, worked out once per strip (one lane per step) instead of by every wavefront in every step: the scalar
       // arithmetic of a step -- window rows, ring slot (a modulo), bucket bounds -- was ~330 clock ticks on every evaluating wavefront's
-      // chain and more on the loaders', much of it reloads of spilled scalars.
-      int crowded = 0;  // does any cell of this strip hold more entries than a slice buffer (the loaders' overflow() path)?
+      // chain and more on the loaders', much of it reloads of spilled scalars.  One workgroup barrier inside; returns whether any cell of the
+      // strip holds more entries than a slice buffer (uniform: the loaders skip overflow()'s per-step look-up otherwise).
+      auto set_up_records = [&]() {
+      int crowded = 0;
       for (int cy = tid; cy < a.cell_rows; cy += kAll) {
         const int b = cy * a.cells_per_row + cx;
         const int4 sg = make_int4(groups ? group_off[b] : 0, groups ? group_off[b + 1] : 0, cands ? cand_off[b] : 0, cands ? cand_off[b + 1] : 0);
@@ -771,46 +753,28 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
         const int sh = min(cy * a.sb_h + a.sb_h, a.s_ymax) - cy * a.sb_h;
         const bool ok = strip_ok && wy1 - wy0 >= H && sh >= H;
         const unsigned wh_ok = strip_ok && wy1 - wy0 >= H ? (unsigned)(wy1 - wy0 - H) : 0u;
-        wins[cy] = make_int4(wy0, (wy0 - a.ymin) % a.R, (int)wh_ok, (int)(((unsigned)(sh - H) & 0x7fffffffu) | (ok ? 0x80000000u : 0u)));
-        const int ya = cy > 0 ? win_y1(cy - 1) : win_y0(0);
-        bats[cy] = make_int4(ya, wy1 - ya, sh, ((ya - a.ymin) % a.R) * a.pitch);
+        wins[cy] = make_int4(wy0, (wy0 - y_first) % a.R, (int)wh_ok, (int)(((unsigned)(sh - H) & 0x7fffffffu) | (ok ? 0x80000000u : 0u)));
+        const int ya = cy > 0 ? win_y1(cy - 1) : y_first + n_fill * fill_h;  // (batch 0: what the fill batches leave of the first window)
+        bats[cy] = make_int4(ya, wy1 - ya, sh, ((ya - y_first) % a.R) * a.pitch);
       }
       // (an OR over the workgroup through 16 words of the flag area: __syncthreads_or() brings its own static LDS, and the widest cells
       // leave none)
       if (lane == 0) misc[16 + wave] = __ballot(crowded != 0) != 0 ? 1 : 0;
       __syncthreads();
-      bool any_crowded;  // (uniform: the loaders skip overflow()'s per-step look-up otherwise)
-      {
-        const int4 *f = reinterpret_cast<const int4 *>(misc + 16);
-        const int4 f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
-        any_crowded = uni((f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z | f2.w | f3.x | f3.y | f3.z | f3.w)) != 0;
-      }
-      // ---- prologue of the strip: the whole first window in passes of what the staging registers hold, the first source
-      // cell and list slices (every wavefront of the workgroup takes part: nothing to evaluate yet)
-      SB_T(p0);
-      {
-        Stage st0;
-        const int rows_per_pass = (kRingN * kAll) / a.cpr;
-        const Batch b = batch_of(0);
-        for (int ya = win_y0(0); ya < win_y1(0); ya += rows_per_pass) {
-          Batch p = b;
-          p.ya = ya; p.yb = min(ya + rows_per_pass, win_y1(0));
-          if (ya != win_y0(0)) { p.ns = 0; p.ng = 0; p.nc = 0; }
-          int me = tid;
-          asm volatile("" : "+v"(me));  // (as in overflow() below: nothing of this loop is worth keeping across the strip)
-          request_gen(p, st0, me, kAll);
-          commit_gen(p, st0, me, kAll);
-        }
-      }
+      const int4 *f = reinterpret_cast<const int4 *>(misc + 16);
+      const int4 f0 = f[0], f1 = f[1], f2 = f[2], f3 = f[3];
+      return uni((f0.x | f0.y | f0.z | f0.w | f1.x | f1.y | f1.z | f1.w | f2.x | f2.y | f2.z | f2.w | f3.x | f3.y | f3.z | f3.w)) != 0;
+      };
       // The two roles run their own step loops with the same sequence of workgroup barriers.  The loader's loop body is
       // straight-line around the registers that are in flight across the barrier (commit, then request): any join
       // with a live staged register makes the compiler copy it -- and wait for it -- on the spot.
-      // Steady-state transport of the loader lanes: a batch always has the same shape (sb_h rows below the previous one),
-      // so each lane's chunk offsets are computed once per strip and a staged load costs a compare, a select and the load
-      // (scalar base + 32-bit lane offset).  The general forms above cost ~25 instructions per chunk, and with ~14 chunks
-      // per lane that made the loaders, not the memory system or the evaluation, the longest thing in a step.
+      // Transport of the loader lanes: a batch always has the same shape (at most fill_h rows below the previous one, the fill batches
+      // of the first window included), so each lane's chunk offsets are computed once per strip and a staged load costs a compare, a select and the load
+      // (scalar base + 32-bit lane offset).  General forms (a division per chunk, ~25 instructions) made the loaders, not the
+      // memory system or the evaluation, the longest thing in a step -- and, run by all 1024 lanes as a prologue for the first window,
+      // cost an item ~10 500 clock ticks in which nothing overlapped (profiles/sad_strip_stream.md).
       unsigned r_goff[kRingN], r_loff[kRingN], s_goff[kSrcN], s_loff[kSrcN];
-      int lt_s = lt;  // (opaque: the tables below must not be computed -- and kept alive -- across the prologue above)
+      int lt_s = lt;  // (opaque: the tables below must not be hoisted out of the item loop and kept alive across other items' walks)
       asm volatile("" : "+v"(lt_s));
 #pragma unroll
       for (int i = 0; i < kRingN; ++i) {
@@ -871,20 +835,25 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
         for (int i = 0; i < kCN; ++i)
           if (lt + i * kLT < b.nc * 2) *reinterpret_cast<uint32_t *>(lds + cdesc_off_of(b.buf) + (lt + i * kLT) * 4) = st.c[i];
       };
-      const int steps = (dbg & 256) ? 0 : (a.cell_rows + 1) & ~1;  // both roles run an even number of steps (the odd one out only meets the barriers); (dbg 256: timing ablation, prologue only)
+      // Positions cy_first .. : n_fill + 1 of them bring the first window in (the evaluating wavefronts only meet the barrier), then one per
+      // cell.  The loader groups take them in pairs; an odd last position has nothing left to request.  (dbg 256: timing ablation, fill
+      // positions only)
+      const int cy_first = -(n_fill + 1), cy_end = (dbg & 256) ? 0 : a.cell_rows;
+      const int cy_tail = cy_first + ((cy_end - cy_first) & ~1);  // the odd position out, if < cy_end
       if constexpr (kLoader) {
         // Two loader groups take alternate steps: during step cy the group of that parity writes batch cy + 1 (which it requested
         // during step cy - 1) to LDS while the other group requests batch cy + 2, so a batch -- ~30 KB per CU -- has a whole step to
         // arrive and each wavefront only ever waits for its own loads (with two batches in one wavefront the compiler's vmcnt
         // bookkeeping drained the younger batch too).  Each group's loop is straight-line around the staged registers.
         Stage st;
+        bool any_crowded = false;
         auto overflow = [&](int cy, bool mine) {  // a crowded bucket: further slices through the same buffers
-          if (cy >= a.cell_rows) return;
+          if (cy < 0) return;  // (a fill position: the evaluating wavefronts only meet its barrier)
           const Seg cur = seg_of(cy);
           int g = cur.g0 + min(cur.g1 - cur.g0, a.gcap), c = cur.c0 + min(cur.c1 - cur.c0, a.ccap);
           while (g < cur.g1 || c < cur.c1) {
             Batch o;
-            o.ya = o.yb = win_y0(0); o.sy0 = 0; o.ns = 0; o.buf = cy & 1;
+            o.ya = o.yb = y_first; o.sy0 = 0; o.ns = 0; o.first = 0; o.buf = cy & 1;
             o.g0 = g; o.ng = min(cur.g1 - g, a.gcap); o.c0 = c; o.nc = min(cur.c1 - c, a.ccap);
             __syncthreads();  // the evaluating wavefronts are done with the previous slice
             if (mine) {
@@ -892,9 +861,9 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
               // hoisted out of the step loop and stays in registers -- or in scratch -- for the whole strip)
               int me = lt;
               asm volatile("" : "+v"(me));
-              Stage so;
-              request_gen(o, so, me, kLT);
-              commit_gen(o, so, me, kLT);
+              Words so;
+              request_lists(o, so, me, kLT);
+              commit_lists(o, so, me, kLT);
             }
             __syncthreads();
             g += o.ng; c += o.nc;
@@ -904,7 +873,17 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
         // group writes -- it works out and requests the batch it will write next (cy + 2 seen from the passive step).  Doing both in the
         // active step (the first form) made one wavefront's commit -> bookkeeping -> request sequence, ~4400 clock ticks, the longest
         // thing in a step, with the other group idle and the evaluating wavefronts (~3700) waiting at the barrier for it.
-        Batch held = batch_of(0);
+        // The records are set up BEHIND the first request where that is a fill batch (described by scalars alone): the bucket bounds' trip
+        // to global memory and the barrier then pass while the first rows of the window are on their way.  (Loader lanes load nothing in
+        // set_up_records() unless a strip has more cells than there are evaluating lanes, so nothing queues up behind the staged loads.
+        // In a taller strip they do, between group 0's request and its first commit: vector memory returns in order, so the bucket bounds
+        // only come back once the staged rows have, and that item's first position waits out both round trips one after the other -- a
+        // cost in time, never in correctness, and no join around the staged registers: the loop in set_up_records() touches none.)
+        if (n_fill == 0) any_crowded = set_up_records();
+        // (With n_fill > 0 this batch_of() runs BEFORE the records of this item exist: it reads segs[0] / bats[0] as the previous item left
+        // them, or as LDS came up for a workgroup's first item.  A fill batch takes its rows from scalars alone and has ng = nc = ns = 0;
+        // the stale g0 / c0 only pick which in-bounds list word request()'s clamped dummy loads re-read, and commit() stores none of them.)
+        Batch held = batch_of(cy_first + 1);
         auto active = [&](int cy) {
           if (dbg & 64) { __syncthreads(); return; }  // (timing ablation: barriers only)
           SB_T(l0);
@@ -935,28 +914,35 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
           SB_ACC(3, q1, q0); SB_ACC(6, q2, q1); SB_WAIT(q2, q1);
         };
         if (grp == 0) {
-          held = batch_of(1);
-          request(held, st);
-          __syncthreads();
-          for (int cy = 0; cy < steps; cy += 2) {
+          request(held, st);  // the first batch of the item (a fill batch unless the first window is one batch high)
+          if (n_fill > 0) any_crowded = set_up_records();
+          for (int cy = cy_first; cy < cy_tail; cy += 2) {
             active(cy);
             passive(cy + 1);
           }
+          if (cy_tail < cy_end) active(cy_tail);
         } else {
-          __syncthreads();
-          for (int cy = 0; cy < steps; cy += 2) {
+          if (n_fill > 0) any_crowded = set_up_records();
+          for (int cy = cy_first; cy < cy_tail; cy += 2) {
             passive(cy);
             active(cy + 1);
           }
+          if (cy_tail < cy_end) {  // (passive() without a request: no batch is left)
+            if (any_crowded) overflow(cy_tail, false);
+            __syncthreads();
+          }
         }
       } else {
-        __syncthreads();
-        SB_T(p1);
-        SB_ACC(5, p1, p0); SB_ACC(6, 1, 0);
-        for (int cy = 0; cy < steps; ++cy) {
-          if (cy >= a.cell_rows) {  // (the padding step of an odd walk)
+        set_up_records();
+        SB_T(p0);
+        for (int cy = cy_first; cy < cy_end; ++cy) {
+          if (cy < 0) {  // a fill position: the first window is on its way, nothing to evaluate yet
             __syncthreads();
-            break;
+            if (cy == -1) {
+              SB_T(p1);
+              SB_ACC(5, p1, p0); SB_ACC(6, 1, 0);
+            }
+            continue;
           }
           if (dbg & (64 | 2048)) { __syncthreads(); continue; }  // (2048: timing ablation, the evaluators skip their bookkeeping too)
           const int buf = cy & 1;
@@ -1023,7 +1009,6 @@ __global__ __launch_bounds__(C::kAll) void sad_strip_kernel(PlaneView<T> src, Pl
 struct SbLaunch {
   hipStream_t stream;
   int grid, threads, upl;
-  bool deep;  // CfgDeep
   size_t lds_bytes;
   StripArgs a;
   const aomhip_sad_x4d_cand *groups;
@@ -1055,19 +1040,8 @@ static int launch_nt(const SbLaunch &l, const PlaneView<T> &s, const PlaneView<T
   return AOMHIP_OK;
 }
 
-// The deep configuration is an experiment (AOMHIP_SB_CFG=deep, 16x16 on 8-bit planes only): its evaluation is ~25 % shorter per step,
-// but four loader wavefronts cannot carry a step's transport (15 chunks per lane: the commit sequence alone outlasts the evaluation).
-constexpr bool deep_size(int es, int w, int h) { return es == 1 && w == 16 && h == 16; }
-inline bool use_deep(int es, int w, int h, bool skip) {
-  if (!deep_size(es, w, h) || skip) return false;
-  const char *e = getenv("AOMHIP_SB_CFG");
-  return e && e[0] == 'd';
-}
 template <typename T, int W, int H, bool SKIP>
 static int launch(const SbLaunch &l, const PlaneView<T> &s, const PlaneView<T> &r) {
-  if constexpr (deep_size((int)sizeof(T), W, H) && !SKIP) {
-    if (l.deep) return launch_nt<T, W, H, SKIP, CfgDeep>(l, s, r);
-  }
   return launch_nt<T, W, H, SKIP, CfgWide>(l, s, r);
 }
 
@@ -1176,11 +1150,8 @@ static int sb_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_plan
   a.R = 2 * sb_h + 2 * range;
   a.scpr = (sb_w * es + 15) / 16 + (((sb_w % epc) == 0 && (src->border % epc) == 0) ? 0 : 1);
   a.spitch = ((a.scpr & 3) == 0 ? a.scpr + 1 : a.scpr) * 16;
-  l.deep = sb::use_deep(es, bw, bh, (flags & AOMHIP_SAD_SKIP_ROWS) != 0);
-  const int ring_chunks = l.deep ? sb::CfgDeep::kRingN * sb::CfgDeep::kLT : sb::CfgWide::kRingN * sb::CfgWide::kLT;
-  const int src_chunks = l.deep ? sb::CfgDeep::kSrcN * sb::CfgDeep::kLT : sb::CfgWide::kSrcN * sb::CfgWide::kLT;
-  const int g_words = l.deep ? sb::CfgDeep::kGN * sb::CfgDeep::kLT : sb::CfgWide::kGN * sb::CfgWide::kLT;
-  const int c_words = l.deep ? sb::CfgDeep::kCN * sb::CfgDeep::kLT : sb::CfgWide::kCN * sb::CfgWide::kLT;
+  const int ring_chunks = sb::CfgWide::kRingN * sb::CfgWide::kLT, src_chunks = sb::CfgWide::kSrcN * sb::CfgWide::kLT;
+  const int g_words = sb::CfgWide::kGN * sb::CfgWide::kLT, c_words = sb::CfgWide::kCN * sb::CfgWide::kLT;
   if (sb_h * a.cpr > ring_chunks || sb_h * a.scpr > src_chunks) {
     set_error("a step of %d rows x (%d + %d) bytes exceeds what the loader wavefronts keep in flight (%d + %d KB): use a lower cell",
               sb_h, a.cpr * 16, a.scpr * 16, ring_chunks / 64, src_chunks / 64);

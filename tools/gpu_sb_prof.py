@@ -42,7 +42,7 @@ def main():
                           "loader_per_active_step_cycles": {"batch_of(cy+1)": p[8] / lsteps, "commit(incl. wait)": p[9] / lsteps, "wait_for_loads": p[15] / lsteps, "overflow+batch_of(cy+3)": p[10] / lsteps,
                                                             "request(+batch_of)": p[11] / lsteps, "barrier": p[12] / lsteps, "passive_overflow+barrier": p[14] / lsteps},
                           "raw_first_wavefront_per_step": [round(p[i] / steps) for i in range(4)],
-                          "prologue_cycles_per_item": p[5] / items,
+                          "fill_position_cycles_per_item": p[5] / items,
                           "barrier_wait_per_step_by_wavefront": [round(x / steps) for x in p[16:32]]}), flush=True)
         for d in (d_gs, d_cs, d_off): ctx.free(d)
 main()
