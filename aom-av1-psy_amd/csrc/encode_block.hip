@@ -44,7 +44,7 @@ __global__ __launch_bounds__(eb_threads<W>()) void encode_inter_block_kernel(Pla
   constexpr bool HBD = sizeof(T) == 2;
   constexpr int BPW = eb_threads<W>() / W;   // blocks per workgroup
   constexpr int NC = W * H;
-  constexpr int LS = (NC > 256) + (NC > 1024);
+  constexpr int LS = tx_scale(W, H);
   constexpr int LSTRIDE = W + 1;
   constexpr int TILE = (H * LSTRIDE + 3) & ~3;
   // av1_gen_inv_stage_range (av1_inv_txfm2d.c:188-232)
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(eb_threads<W>()) void encode_inter_block_kernel(Pla
 #pragma unroll
     for (int r = 0; r < H; ++r) x[r] = 0;
   }
-  const bool fast = group_max<W>(amax) <= kSafeMax[tx_index_of(W, H)][tx_type & 15];
+  const bool fast = group_max<W>(amax) <= kSafeMax[tx_size_of(W, H)][tx_type & 15];
 
   // ---- 3. forward columns -> transpose tile D
   if (live) {
@@ -154,9 +154,8 @@ __global__ __launch_bounds__(eb_threads<W>()) void encode_inter_block_kernel(Pla
   block_sync();   // D (the tile) is dead from here: it becomes the dqcoeff staging area
   if (live) {
     fwd_1d_sel<W, C::cos_bit_row>(y, hk == 2 ? 1 : hk, fast);
-    const int scan_class = tx_type < 10 ? 0 : ((tx_type & 1) ? 2 : 1);
-    const int zb[2] = { (qa.zbin[0] + ((1 << LS) >> 1)) >> LS, (qa.zbin[1] + ((1 << LS) >> 1)) >> LS };
-    const int rd[2] = { (qa.round[0] + ((1 << LS) >> 1)) >> LS, (qa.round[1] + ((1 << LS) >> 1)) >> LS };
+    const int scan_class = scan_class_of(tx_type);
+    const int zb[2] = { log_scaled<LS>(qa.zbin[0]), log_scaled<LS>(qa.zbin[1]) }, rd[2] = { log_scaled<LS>(qa.round[0]), log_scaled<LS>(qa.round[1]) };
     int last_c = -1;
 #pragma unroll
     for (int c = 0; c < W; ++c) {

@@ -177,29 +177,7 @@ template <int W, int H, int BD, typename PIX> static int launch_inv(const InvLau
 }
 
 template <int BD, typename PIX> static int dispatch_inv(int tx_size, const InvLaunch &l) {
-  switch (tx_size) {
-    case 0: return launch_inv<4, 4, BD, PIX>(l);
-    case 1: return launch_inv<8, 8, BD, PIX>(l);
-    case 2: return launch_inv<16, 16, BD, PIX>(l);
-    case 3: return launch_inv<32, 32, BD, PIX>(l);
-    case 4: return launch_inv<64, 64, BD, PIX>(l);
-    case 5: return launch_inv<4, 8, BD, PIX>(l);
-    case 6: return launch_inv<8, 4, BD, PIX>(l);
-    case 7: return launch_inv<8, 16, BD, PIX>(l);
-    case 8: return launch_inv<16, 8, BD, PIX>(l);
-    case 9: return launch_inv<16, 32, BD, PIX>(l);
-    case 10: return launch_inv<32, 16, BD, PIX>(l);
-    case 11: return launch_inv<32, 64, BD, PIX>(l);
-    case 12: return launch_inv<64, 32, BD, PIX>(l);
-    case 13: return launch_inv<4, 16, BD, PIX>(l);
-    case 14: return launch_inv<16, 4, BD, PIX>(l);
-    case 15: return launch_inv<8, 32, BD, PIX>(l);
-    case 16: return launch_inv<32, 8, BD, PIX>(l);
-    case 17: return launch_inv<16, 64, BD, PIX>(l);
-    case 18: return launch_inv<64, 16, BD, PIX>(l);
-  }
-  set_error("bad tx_size %d", tx_size);
-  return AOMHIP_ERR_INVALID;
+  return with_tx_size(tx_size, [&](auto w, auto h) { return launch_inv<w, h, BD, PIX>(l); });
 }
 
 }  // namespace aomhip

@@ -1,8 +1,10 @@
-// Device helpers shared by the transform + quantise kernels (xform_quant.hip) and the fused block kernel (encode_block.hip): the
-// coefficient stores, QuantArgs + quantize_one (aom_quantize_b_helper_c / aom_highbd_quantize_b_helper_c / the fp family for one
-// coefficient), the arithmetic inverse scan position, the per-TX_TYPE 1-D kinds, the fast-butterfly bound and the lane-group maximum.
+// Device helpers shared by the transform + quantise kernels (xform_quant.hip, quant_batch.hip, quant_rtcd.hip, txb_cost.hip) and the fused
+// block kernel (encode_block.hip): the coefficient stores, QuantArgs + quantize_one (aom_quantize_b_helper_c / aom_highbd_quantize_b_helper_c /
+// the fp family for one coefficient), the arithmetic inverse scan position, the fast-butterfly bound, the lane-group maximum, the
+// wave-per-block prologue and the row pass + quantise loop.
 #pragma once
 #include "common.h"
+#include "tx_size.h"
 #include "txfm_device.h"
 
 namespace aomhip {
@@ -39,6 +41,12 @@ struct QuantArgs {
   int8_t qs_log2[2];  // log2(quant_shift) when it is a power of two (it always is out of invert_quant,
                       // av1_quantize.c:580-588), else -1 -> generic 64-bit path
 };
+// ROUND_POWER_OF_TWO(v, log_scale): how the log-scaled quantisers take their zbin and round entries
+template <int LS> __device__ __forceinline__ int log_scaled(int v) { return (v + ((1 << LS) >> 1)) >> LS; }
+// the adaptive quantiser's dead-zone widening ROUND_POWER_OF_TWO(dequant * factor, 7): factor EOB_FACTOR(325) for the pre-scan, the same plus
+// SKIP_EOB_FACTOR_ADJUST(200) for the lone +-1 (aom_dsp/quantize.c:36-46,84-102)
+constexpr int kEobFactor = 325, kSkipEobFactor = 325 + 200;
+__device__ __forceinline__ int adaptive_zone(int dequant, int factor) { return (dequant * factor + 64) >> 7; }
 
 // aom_quantize_b_helper_c / aom_highbd_quantize_b_helper_c (aom_dsp/quantize.c:139-166,293-313) for one
 // coefficient, qm == NULL (wt = iwt = 32), branch-free.  Exact re-associations used for the low-bd form:
@@ -176,36 +184,10 @@ template <int KW, int KH> __device__ __forceinline__ int iscan_pos(int r, int c,
   return before + (up ? c - cmin : r - rmin);
 }
 
-// per-TX_TYPE vertical / horizontal 1-D kinds (common_data.h:149-159): 0 DCT 1 ADST 2 FLIPADST 3 IDTX
-__device__ constexpr uint8_t kVKind[16] = { 0, 1, 0, 1, 2, 0, 2, 1, 2, 3, 0, 3, 1, 3, 2, 3 };
-__device__ constexpr uint8_t kHKind[16] = { 0, 0, 1, 1, 0, 2, 2, 2, 1, 3, 3, 0, 3, 1, 3, 2 };
-// ... and of the inverse transform (the same table: av1_inv_txfm2d.c reads vtx_tab / htx_tab too)
-__device__ constexpr uint8_t kIVKind[16] = { 0, 1, 0, 1, 2, 0, 2, 1, 2, 3, 0, 3, 1, 3, 2, 3 };
-__device__ constexpr uint8_t kIHKind[16] = { 0, 0, 1, 1, 0, 2, 2, 2, 1, 3, 3, 0, 3, 1, 3, 2 };
-
-// The same four tables as 2-bit fields of one 32-bit constant each: `kVKind[tx_type]` with a block's own type is an index into constant MEMORY (a vector load
-// behind the record's load at the head of every transform kernel); a shift and a mask of an immediate are not.
-constexpr uint32_t pack_kinds(const uint8_t (&t)[16]) {
-  uint32_t v = 0;
-  for (int i = 0; i < 16; ++i) v |= (uint32_t)(t[i] & 3) << (2 * i);
-  return v;
-}
-__device__ __forceinline__ int v_kind(int tx_type) { return (int)((pack_kinds(kVKind) >> (2 * (tx_type & 15))) & 3u); }
-__device__ __forceinline__ int h_kind(int tx_type) { return (int)((pack_kinds(kHKind) >> (2 * (tx_type & 15))) & 3u); }
-__device__ __forceinline__ int iv_kind(int tx_type) { return (int)((pack_kinds(kIVKind) >> (2 * (tx_type & 15))) & 3u); }
-__device__ __forceinline__ int ih_kind(int tx_type) { return (int)((pack_kinds(kIHKind) >> (2 * (tx_type & 15))) & 3u); }
-
 // Largest residual magnitude per [TX_SIZE][TX_TYPE] under which the fast butterfly is exact (txfm_device.h: kFastBtf)
 __device__ constexpr int16_t kSafeMax[19][16] = {
 #include "txfm_safe_max.inc"
 };
-constexpr int tx_index_of(int w, int h) {  // TX_SIZE (av1/common/enums.h:174-197) of a w x h transform
-  constexpr int tw[19] = { 4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64 };
-  constexpr int th[19] = { 4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16 };
-  for (int i = 0; i < 19; ++i)
-    if (tw[i] == w && th[i] == h) return i;
-  return 0;
-}
 #ifndef AOMHIP_XQ_FAST_BTF
 #define AOMHIP_XQ_FAST_BTF 1   // 0: every block takes the exact butterfly (A/B: profiles/history_r02_r04.md)
 #endif
@@ -230,6 +212,18 @@ template <int LPB> __device__ __forceinline__ int64_t group_sum64(int64_t v) {
   for (int m = 1; m < LPB; m <<= 1) v += __shfl_xor((long long)v, m, 64);
   return v;
 }
+// The prologue of the one-wavefront-per-block kernels (four blocks per 256-thread workgroup) on NC coefficients per block: false past the end
+// of the list, else the block, this lane, the block's type and where its coefficients start.
+struct WaveBlock { int bi, lane, tx_type; int64_t off; };
+template <int NC> __device__ __forceinline__ bool wave_block(const aomhip_txb *__restrict__ blocks, int n_blocks, int uniform_type, WaveBlock &b) {
+  b.lane = threadIdx.x & 63;
+  b.bi = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (b.bi >= n_blocks) return false;
+  b.tx_type = blocks ? blocks[b.bi].tx_type : uniform_type;
+  b.off = blocks ? (int64_t)blocks[b.bi].out_offset : (int64_t)b.bi * NC;
+  return true;
+}
+
 // one term pair of av1_block_error_c / av1_highbd_block_error_c (av1/encoder/rdopt.c:635-682): err_shift < 0 selects the
 // low-bd form, whose products are 32-bit (`diff * diff` on int operands wraps exactly as the compiled reference does)
 __device__ __forceinline__ void block_err_acc(int32_t c, int32_t dq, int err_shift, int64_t &e, int64_t &z) {
@@ -284,6 +278,34 @@ __device__ __forceinline__ void block_sync() {
 #else
   __syncthreads();
 #endif
+}
+
+// The row pass of the fused kernels for the lane that holds row r of a W x H block (y: the row out of the transpose tile): the W-point network,
+// the last two shifts of av1_fwd_txfm2d's round_shift_array calls, the rectangular sqrt(2), aom_quantize_b on the KW coded coefficients.
+// sink(c, rc, v, qv, dqv) takes coefficient (r, c) -- rc = c * KH + r, its index in the reference's transposed layout -- and its level.
+// (A sink captures its output pointers by value: through a by-reference capture they lose `__restrict__`, which costs the 64x16 kernels 43 VGPRs.)
+// Returns the lane's end-of-block candidate: the inverse scan position grows with c along a row, so only the last non-zero c matters.
+template <int W, int H, bool HBD, typename Sink>
+__device__ __forceinline__ int row_pass_quantize(int32_t (&y)[W], int r, int tx_type, bool fast, const QuantArgs &qa, Sink &&sink) {
+  using C = Cfg2D<W, H>;
+  constexpr int KW = tx_coded(W), KH = tx_coded(H), LS = tx_scale(W, H);
+  const int hk = h_kind(tx_type);
+  fwd_1d_sel<W, C::cos_bit_row>(y, hk == 2 ? 1 : hk, fast);
+  const int scan_class = scan_class_of(tx_type);
+  const int zb[2] = { log_scaled<LS>(qa.zbin[0]), log_scaled<LS>(qa.zbin[1]) }, rd[2] = { log_scaled<LS>(qa.round[0]), log_scaled<LS>(qa.round[1]) };
+  int last_c = -1;
+#pragma unroll
+  for (int c = 0; c < KW; ++c) {
+    int32_t v = y[c];
+    if constexpr (C::fs2 < 0) v = rshift(v, -C::fs2);
+    if constexpr (C::rect2) v = rshift64((int64_t)v * kSqrt2, kSqrt2Bits);
+    const int ac = (c == 0) ? (r != 0) : 1;  // DC is (r, c) == (0, 0)
+    int32_t qv, dqv;
+    quantize_one<HBD, LS>(v, zb[ac], rd[ac], qa.quant[ac], qa.quant_shift[ac], qa.qs_log2[ac], qa.dequant[ac], &qv, &dqv);
+    last_c = qv ? c : last_c;
+    sink(c, c * KH + r, v, qv, dqv);
+  }
+  return last_c >= 0 ? iscan_pos<KW, KH>(r, last_c, scan_class) + 1 : 0;
 }
 
 // QuantArgs of a parameter block (quant_kind 1: the av1_quantize_fp family)

@@ -6,6 +6,7 @@
 // default context, the batched entry points' device code; a failed call records the sticky status, zeroes the coefficient-like outputs
 // whose extent it knows, leaves pixels untouched and returns (a block error returns AOMHIP_FAILED_BLOCK_ERROR); it never aborts.
 #include "common.h"
+#include "tx_size.h"
 
 namespace aomhip {
 
@@ -30,13 +31,6 @@ __global__ __launch_bounds__(256) void copy_to_u16_kernel(const S *__restrict__ 
   if (i < n) dst[i] = src[i];
 }
 
-static constexpr int kW[19] = { 4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64 };
-static constexpr int kH[19] = { 4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16 };
-static constexpr int tx_index(int w, int h) {
-  for (int t = 0; t < 19; ++t)
-    if (kW[t] == w && kH[t] == h) return t;
-  return -1;
-}
 
 static bool fail_invalid(const char *who, const char *fmt, long v) {
   char msg[160];
@@ -64,7 +58,7 @@ static bool param_ok(const char *who, const aomhip_txfm_param *p, int tx_size, b
     if (p->tx_type != 0) return fail_invalid(who, "lossless with tx_type %ld (DCT_DCT only)", p->tx_type);
   } else if (!tx_type_ok(tx_size, p->tx_type)) {
     char what[96];
-    snprintf(what, sizeof(what), "no %dx%d transform of tx_type %%ld", kW[tx_size], kH[tx_size]);
+    snprintf(what, sizeof(what), "no %dx%d transform of tx_type %%ld", kTxWide[tx_size], kTxHigh[tx_size]);
     return fail_invalid(who, what, p->tx_type);
   }
   return true;
@@ -76,7 +70,7 @@ static bool param_ok(const char *who, const aomhip_txfm_param *p, int tx_size, b
 static void inv_add(const char *who, const int32_t *input, void *dst, int stride, size_t esz, int tx_size, int type, int bd, int wht_eob) {
   aomhip_ctx *ctx = default_ctx();
   if (!ctx) return;
-  const int w = kW[tx_size], h = kH[tx_size], nc = aomhip_tx_max_eob(tx_size);
+  const int w = kTxWide[tx_size], h = kTxHigh[tx_size], nc = aomhip_tx_max_eob(tx_size);
   // the batched entry types its planes by bit depth: bd 8 runs on uint8 pixels (av1_inv_txfm_add_c: the same arithmetic on a uint16 copy)
   const size_t pe = bd == 8 ? 1 : 2;
   const size_t pix_bytes = ((size_t)w * h * pe + 255) & ~(size_t)255, c_off = pix_bytes, e_off = c_off + (size_t)nc * 4, total = e_off + 16;
@@ -186,7 +180,7 @@ void aomhip_highbd_inv_txfm_add(const int32_t *input, uint8_t *dest, int stride,
 }
 #define AOMHIP_HBD_INV(W, H)                                                                                          \
   void aomhip_highbd_inv_txfm_add_##W##x##H(const int32_t *input, uint8_t *dest, int stride, const void *txfm_param) { \
-    inv_txfm_add_any("aomhip_highbd_inv_txfm_add_" #W "x" #H, input, hbd_ptr(dest), stride, 2, txfm_param, tx_index(W, H)); \
+    inv_txfm_add_any("aomhip_highbd_inv_txfm_add_" #W "x" #H, input, hbd_ptr(dest), stride, 2, txfm_param, tx_size_of(W, H)); \
   }
 AOMHIP_RTCD_TX_SIZES(AOMHIP_HBD_INV)
 #undef AOMHIP_HBD_INV
@@ -205,7 +199,7 @@ void aomhip_lowbd_fwd_txfm(const int16_t *src_diff, int32_t *coeff, int diff_str
   const int tx = p ? p->tx_size : -1;
   if (tx >= 0 && tx < 19) memset(coeff, 0, (size_t)aomhip_tx_max_eob(tx) * 4);
   if (!param_ok(who, p, tx, false)) return;
-  aomhip_fwd_txfm2d(src_diff, coeff, diff_stride, p->lossless ? AOMHIP_TX_WHT : p->tx_type, p->bd, kW[tx], kH[tx]);
+  aomhip_fwd_txfm2d(src_diff, coeff, diff_stride, p->lossless ? AOMHIP_TX_WHT : p->tx_type, p->bd, kTxWide[tx], kTxHigh[tx]);
 }
 void aomhip_fwht4x4(const int16_t *input, int32_t *output, int stride) { aomhip_fwd_txfm2d(input, output, stride, AOMHIP_TX_WHT, 8, 4, 4); }
 

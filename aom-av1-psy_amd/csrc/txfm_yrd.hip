@@ -13,6 +13,7 @@
 // the early exits never trigger.  Blocks lie wholly inside the frame (mb_to_right_edge / mb_to_bottom_edge >= 0).
 #include "common.h"
 #include "search_chain.h"
+#include "tx_size.h"
 
 namespace aomhip {
 namespace {
@@ -89,14 +90,6 @@ __global__ __launch_bounds__(256) void yrd_finish_kernel(const aomhip_txfm_yrd_b
   out[i].rd = rd; out[i].dist = dist; out[i].sse = v.sse; out[i].rate = (int32_t)rate; out[i].skip_txfm = skip;
 }
 
-int tx_size_of(int w, int h) {
-  static const int tw[19] = { 4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64 };
-  static const int th[19] = { 4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16 };
-  for (int i = 0; i < 19; ++i)
-    if (tw[i] == w && th[i] == h) return i;
-  return -1;
-}
-
 struct YrdMem {   // the composite's work memory for n blocks of nc coefficients per transform block
   aomhip_txb *txb; int32_t *coeff, *q, *dq, *cost; uint16_t *eob; int64_t *err; uint8_t *tctx, *ectx, *run; YrdAcc *acc;
   void carve(WorkCarver &c, size_t n, size_t nc) {
@@ -119,8 +112,7 @@ int estimate_txfm_yrd_ws(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip
   const int txw = bw > 64 ? 64 : bw, txh = bh > 64 ? 64 : bh;
   const int tx_size = tx_size_of(txw, txh);
   const int nc = aomhip_tx_max_eob(tx_size);
-  const int pels = txw * txh, scale = (pels > 256) + (pels > 1024);
-  const int shift = (1 - scale) * 2;   // (MAX_TX_SCALE - av1_get_tx_scale(tx_size)) * 2
+  const int shift = (1 - tx_scale(txw, txh)) * 2;   // (MAX_TX_SCALE - av1_get_tx_scale(tx_size)) * 2
   YrdMem m;
   WorkCarver c{ ws };
   m.carve(c, (size_t)n_blocks, (size_t)nc);

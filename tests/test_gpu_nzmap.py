@@ -1,4 +1,4 @@
-"""aomhip_get_nz_map_contexts_batch (csrc/xform_quant.hip) behind aomhip_txb_init_levels_batch against (a) av1_get_nz_map_contexts_c interpreted
+"""aomhip_get_nz_map_contexts_batch (csrc/txb_cost.hip) behind aomhip_txb_init_levels_batch against (a) av1_get_nz_map_contexts_c interpreted
 (tests/golden/ref_eval_nzmap.npz, directly) and (b) the oracle on lists of blocks with mixed transform types."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""aomhip_quantize_b_adaptive_qm_batch (csrc/xform_quant.hip) against (a) the interpreted reference's aom_[highbd_]quantize_b_adaptive_helper_c with
+"""aomhip_quantize_b_adaptive_qm_batch (csrc/quant_batch.hip) against (a) the interpreted reference's aom_[highbd_]quantize_b_adaptive_helper_c with
 qm_ptr / iqm_ptr (tests/golden/ref_eval_qm_adaptive.npz: 180 cases, directly) and (b) the oracle on lists of blocks."""
 import numpy as np
 import pytest

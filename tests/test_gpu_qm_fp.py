@@ -1,4 +1,4 @@
-"""aomhip_quantize_fp_qm_batch (csrc/xform_quant.hip) against (a) the interpreted reference's quantize_fp_helper_c / highbd_quantize_fp_helper_c with
+"""aomhip_quantize_fp_qm_batch (csrc/quant_batch.hip) against (a) the interpreted reference's quantize_fp_helper_c / highbd_quantize_fp_helper_c with
 qm_ptr / iqm_ptr (tests/golden/ref_eval_qm_fp.npz: 140 cases, directly) and (b) the oracle on lists of blocks."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""aomhip_quantize_lp_batch (csrc/xform_quant.hip) against (a) the interpreted reference's av1_quantize_lp_c / av1_block_error_lp_c
+"""aomhip_quantize_lp_batch (csrc/quant_batch.hip) against (a) the interpreted reference's av1_quantize_lp_c / av1_block_error_lp_c
 (tests/golden/ref_eval_quant_lp.npz, directly) and (b) the oracle on lists of blocks, list and grid mode."""
 import json
 

@@ -1,4 +1,4 @@
-"""aomhip_cost_coeffs_txb_batch / _laplacian_batch (csrc/xform_quant.hip) against (a) warehouse_efficients_txb interpreted on random cost tables
+"""aomhip_cost_coeffs_txb_batch / _laplacian_batch (csrc/txb_cost.hip) against (a) warehouse_efficients_txb interpreted on random cost tables
 (tests/golden/ref_eval_txb_cost.npz, directly) and (b) the oracle on lists of blocks with mixed transform types."""
 import numpy as np
 import pytest

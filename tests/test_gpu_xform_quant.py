@@ -120,7 +120,7 @@ def test_fused_subtract(hip, oracle, ctx, bd):
     ctx.planes_upload(ps, 1, src)
     ctx.planes_upload(pp, 1, pred)
     residual = (src.astype(np.int32) - pred.astype(np.int32)).astype(np.int16)  # subtract.c:20-53
-    for tx_size in (0, 2, 3, 7):
+    for tx_size in (0, 2, 3, 5, 7, 13):
         w, h = oracle.TX_W[tx_size], oracle.TX_H[tx_size]
         types = [t for t in range(16) if oracle.lib.orc_txfm_valid(tx_size, t)]
         nc = hip.capi.lib.aomhip_tx_max_eob(tx_size)
