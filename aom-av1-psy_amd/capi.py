@@ -133,6 +133,11 @@ rect_dtype = np.dtype([("h_start", "<i4"), ("h_end", "<i4"), ("v_start", "<i4"),
 lr_unit_info_dtype = np.dtype([("restoration_type", "<i4"), ("sgr_params_idx", "<i4"), ("xqd", "<i4", (2,)), ("hfilter", "<i2", (8,)), ("vfilter", "<i2", (8,))])
 # aomhip_sgr_search_result (24 bytes): one record of aomhip_search_selfguided_restoration_batch
 sgr_search_result_dtype = np.dtype([("ep", "<i4"), ("xqd", "<i4", (2,)), ("visited", "<i4"), ("err", "<i8")])
+# aomhip_wiener_search_result (64 bytes) / aomhip_wiener_trial (16 bytes): the records of aomhip_search_wiener_batch
+WIENER_MAX_TRIALS = 96
+wiener_search_result_dtype = np.dtype([("hfilter", "<i2", (8,)), ("vfilter", "<i2", (8,)), ("sse", "<i8"), ("sse_none", "<i8"), ("score", "<i8"), ("trials", "<i4"),
+                                       ("singular", "<i4")])
+wiener_trial_dtype = np.dtype([("h", "i1", (3,)), ("v", "i1", (3,)), ("pad", "<i2"), ("err", "<i8")])
 scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_qn", "subpel_y_qn", "dst_x", "dst_y")])   # aomhip_scaled_block
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
@@ -284,6 +289,7 @@ _protos = {
     "aomhip_calc_proj_params_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "aomhip_pixel_proj_error_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp]),
     "aomhip_search_selfguided_restoration_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "aomhip_search_wiener_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_wedge_sse_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "aomhip_wedge_sign_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "aomhip_wedge_compute_delta_squares_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
@@ -950,6 +956,14 @@ class Context:
         hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
         check(lib.aomhip_search_selfguided_restoration_batch(self.h, C.byref(src), src_frame, C.byref(dat), dat_frame, d_units, hu, n_units, enable_sgr_ep_pruning,
                                                              d_best, d_per_ep), "aomhip_search_selfguided_restoration_batch")
+
+    def search_wiener_batch(self, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, ss_y, wiener_win, d_units, h_units, n_units, downsample, d_result,
+                            d_trace=None):
+        """search_wiener per restoration unit (rect_dtype records) up to the RD comparison: d_result[i] = the refined filter, its SSE, the SSE without
+        restoration, the score and the trial count (wiener_search_result_dtype), d_trace[i * WIENER_MAX_TRIALS + t] = trial t (wiener_trial_dtype; may be None)."""
+        hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
+        check(lib.aomhip_search_wiener_batch(self.h, C.byref(src), src_frame, C.byref(deblocked), deblocked_frame, C.byref(cdef), cdef_frame, ss_y, wiener_win,
+                                             d_units, hu, n_units, downsample, d_result, d_trace), "aomhip_search_wiener_batch")
 
     def scaled_pred_batch(self, ref, ref_frame, pred, pred_frame, bw, bh, fx, fy, x_step_qn, y_step_qn, d_blocks, n_blocks):
         """av1_[highbd_]convolve_2d_scale for a batch of blocks (scaled_block_dtype records), single reference."""

@@ -28,7 +28,7 @@
 // wiener_kernel of restoration.hip.  RESTORE_NONE (and any other type value): copy.  The arithmetic is that of restoration.hip's kernels
 // (av1_selfguided_restoration + av1_decode_xq + the projection; av1_[highbd_]wiener_convolve_add_src with get_conv_params_wiener(bd)).
 // LDS: 5320 + 2 x 8976 = 23272 bytes, six workgroups per CU by LDS.
-#include "common.h"
+#include "restoration_device.h"
 
 namespace aomhip {
 
@@ -37,22 +37,8 @@ __device__ const int kLrSgrParams[16][4] = AOMHIP_SGR_PARAMS;
 __device__ const int32_t kLrXByXplus1[256] = AOMHIP_X_BY_XPLUS1;
 __device__ const int32_t kLrOneByX[25] = AOMHIP_ONE_BY_X;
 
-#ifndef AOMHIP_LR_PW
-#define AOMHIP_LR_PW 64                                        // 64 or 32 (tools/gpu_lr_frame.py measured both)
-#endif
-constexpr int kLrPW = AOMHIP_LR_PW, kLrPH = 32;                // piece: columns x rows
-static_assert(kLrPW == 64 || kLrPW == 32, "a wavefront covers one or two rows of a piece");
-constexpr int kLrFW = kLrPW + 6, kLrFH = kLrPH + 6;            // its footprint
 constexpr int kLrAW = kLrPW + 2, kLrAH = kLrPH + 2;            // positions -1 .. 64 x -1 .. 32 of A[] / B[]
-constexpr int kLrMaxUnit = 384;                                // RESTORATION_UNITSIZE_MAX * 3 / 2: a last unit is < 1.5 unit sizes
-constexpr int kLrPerLane = kLrPW * kLrPH / 256;                // pixels per lane: one column, rows lr_row(tid, 0 .. kLrPerLane - 1)
-
-// Row q of a lane.  All rows of a WAVEFRONT have one parity (the r[0] filter treats even and odd rows differently: no divergence): 64 columns -- a
-// wavefront is a row, rows wave + 4 q; 32 columns -- a wavefront is two rows two apart, rows 8 q + (wave & 1) + 2 * half + 4 * (wave >> 1).
-__device__ __forceinline__ int lr_row(int tid, int q) {
-  if (kLrPW == 64) return (tid >> 6) + 4 * q;
-  return 8 * q + ((tid >> 6) & 1) + 2 * ((tid >> 5) & 1) + 4 * (tid >> 7);
-}
+// (the piece, its footprint, the row rule and the two Wiener passes: restoration_device.h, shared with wiener_search.hip)
 
 template <typename T>
 __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb, int deb_stride, const T *__restrict__ cdef, int cdef_stride,
@@ -86,31 +72,7 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb
   }
 
   // the footprint: rows py0 - 3 .. py1 + 2 through the row rule, columns ox - 3 .. ox + pw + 2 clamped to the plane
-  // (a fixed trip count, unrolled, loads first and LDS stores after: all of a lane's loads are in flight together; rows below a short piece's
-  // footprint load a valid row nobody reads)
-  constexpr int kStage = (kLrFH * kLrFW + 255) / 256;
-  uint16_t staged[kStage];
-#pragma unroll
-  for (int it = 0; it < kStage; ++it) {
-    const int t = min(tid + it * 256, kLrFH * kLrFW - 1);
-    const int fy = t / kLrFW, fx = t - fy * kLrFW;
-    const int y = py0 - 3 + fy, x = min(max(ox - 3 + fx, 0), plane_w - 1);
-    bool from_deb = false;
-    int ry = y;
-    if (y < y0) {
-      from_deb = y0 > 0;
-      ry = from_deb ? max(y, y0 - 2) : 0;
-    } else if (y >= y1) {
-      from_deb = y1 < plane_h;
-      ry = from_deb ? min(y, y1 + 1) : plane_h - 1;
-    }
-    ry = min(max(ry, 0), plane_h - 1);
-    const T *src = from_deb ? deb + (int64_t)ry * deb_stride : cdef + (int64_t)ry * cdef_stride;
-    staged[it] = (uint16_t)src[x];
-  }
-#pragma unroll
-  for (int it = 0; it < kStage; ++it)
-    if (tid + it * 256 < kLrFH * kLrFW) s_d[tid + it * 256] = staged[it];
+  lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, y0, y1, plane_w, plane_h);
   __syncthreads();
   const int mx = (1 << bd) - 1;
 
@@ -197,29 +159,12 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb
   int fh[7], fv[7];
 #pragma unroll
   for (int q = 0; q < 7; ++q) { fh[q] = info[ui].hfilter[q]; fv[q] = info[ui].vfilter[q]; }
-  const int round_0 = bd == 12 ? 5 : 3, round_1 = 14 - round_0;
-  const int limit = (1 << (bd + 8 - round_0)) - 1;   // WIENER_CLAMP_LIMIT
-  for (int t = tid; t < kLrFH * kLrPW; t += 256) {   // temp row r = footprint row r
-    const int r = t / kLrPW, x = t & (kLrPW - 1);
-    if (r >= ph + 6) break;
-    const uint16_t *s = s_d + r * kLrFW + x;   // footprint column x = source column x - 3
-    int sum = ((int)s[3] << 7) + (1 << (bd + 6));
-#pragma unroll
-    for (int q = 0; q < 7; ++q) sum += (int)s[q] * fh[q];
-    s_tmp[t] = (uint16_t)min(max((sum + ((1 << round_0) >> 1)) >> round_0, 0), limit);
-  }
+  lr_wiener_hpass(s_d, s_tmp, tid, ph, fh, bd);
   __syncthreads();
 #pragma unroll
   for (int q = 0; q < kLrPerLane; ++q) {
     const int i = lr_row(tid, q);
-    if (i < ph && lx < pw) {
-      const uint16_t *s = s_tmp + i * kLrPW + lx;   // temp row i = source row i - 3
-      int sum = ((int)s[3 * kLrPW] << 7) - (1 << (bd + round_1 - 1));
-#pragma unroll
-      for (int t = 0; t < 7; ++t) sum += (int)s[t * kLrPW] * fv[t];
-      const int v = (sum + ((1 << round_1) >> 1)) >> round_1;
-      dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)min(max(v, 0), mx);
-    }
+    if (i < ph && lx < pw) dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)lr_wiener_vpixel(s_tmp, i, lx, fv, bd);
   }
 }
 

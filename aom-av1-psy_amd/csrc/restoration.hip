@@ -23,14 +23,16 @@
 namespace aomhip {
 
 constexpr int kBandRows = 16;
-constexpr int kMaxUnit = 256;                      // restoration units are at most 256 pixels wide (RESTORATION_UNITSIZE_MAX)
-constexpr int kTileW = kMaxUnit + 6 + 2;           // + the window margin, padded to an even count
+constexpr int kMaxUnit = 256;                      // restoration units are at most 256 pixels wide (RESTORATION_UNITSIZE_MAX) ...
+constexpr int kMaxUnitWide = 384;                  // ... but for the last one of a row, up to 1.5 of them: the Wiener search's instantiation (wiener_search.hip)
 
-template <typename T, int WIN>
+// MAXW: the widest unit.  The 32-bit band sums hold for 384 too: 4095^2 x 16 rows x 6 column chunks < 2^31.
+template <typename T, int WIN, int MAXW = kMaxUnit>
 __global__ __launch_bounds__(256) void wiener_stats_kernel(const T *__restrict__ dgd, int dgd_stride, const T *__restrict__ src, int src_stride,
                                                            const aomhip_rect *__restrict__ units, int downsample, int divider,
                                                            int64_t *__restrict__ M_out, int64_t *__restrict__ H_out) {
   constexpr int HALF = WIN / 2, WIN2 = WIN * WIN;
+  constexpr int kTileW = MAXW + 6 + 2;             // + the window margin, padded to an even count
   constexpr int NP = WIN * (WIN + 1) / 2;          // column pairs dxa <= dxb
   constexpr int NT = NP + WIN;                     // + the M tasks (column dxa against X)
   constexpr int TG = (NT + 3) / 4;                 // workgroups per unit
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(256) void wiener_stats_kernel(const T *__restrict__
   const int unit = blockIdx.x / TG, task = (blockIdx.x % TG) * 4 + wave;
   const aomhip_rect u = units[unit];
   const int uw = u.h_end - u.h_start, uh = u.v_end - u.v_start;
-  if (uw <= 0 || uh <= 0 || uw > kMaxUnit) return;  // (checked on the host when the caller passes the list there too)
+  if (uw <= 0 || uh <= 0 || uw > MAXW) return;  // (checked on the host when the caller passes the list there too)
 
   // find_average: floor(sum / count)
   unsigned long long s = 0;
@@ -156,15 +158,23 @@ __global__ __launch_bounds__(256) void wiener_stats_kernel(const T *__restrict__
   }
 }
 
-template <typename T>
+template <typename T, int MAXW = kMaxUnit>
 static void launch_stats(hipStream_t st, int win, int n_units, const void *d, int dstride, const void *s, int sstride, const aomhip_rect *units,
                          int downsample, int divider, int64_t *M, int64_t *H) {
   if (win == 7)
-    hipLaunchKernelGGL((wiener_stats_kernel<T, 7>), dim3(n_units * 9), dim3(256), 0, st, static_cast<const T *>(d), dstride,
+    hipLaunchKernelGGL((wiener_stats_kernel<T, 7, MAXW>), dim3(n_units * 9), dim3(256), 0, st, static_cast<const T *>(d), dstride,
                        static_cast<const T *>(s), sstride, units, downsample, divider, M, H);
   else
-    hipLaunchKernelGGL((wiener_stats_kernel<T, 5>), dim3(n_units * 5), dim3(256), 0, st, static_cast<const T *>(d), dstride,
+    hipLaunchKernelGGL((wiener_stats_kernel<T, 5, MAXW>), dim3(n_units * 5), dim3(256), 0, st, static_cast<const T *>(d), dstride,
                        static_cast<const T *>(s), sstride, units, downsample, divider, M, H);
+}
+
+void launch_wiener_stats(hipStream_t stream, int bit_depth, int wiener_win, bool wide, int n_units, const void *dgd, int dgd_stride, const void *src,
+                         int src_stride, const aomhip_rect *d_units, int downsample, int64_t *d_M, int64_t *d_H) {
+  const int divider = bit_depth == 12 ? 16 : bit_depth == 10 ? 4 : 1;
+  auto f = bit_depth == 8 ? (wide ? launch_stats<uint8_t, kMaxUnitWide> : launch_stats<uint8_t>)
+                          : (wide ? launch_stats<uint16_t, kMaxUnitWide> : launch_stats<uint16_t>);
+  f(stream, wiener_win, n_units, dgd, dgd_stride, src, src_stride, d_units, bit_depth == 8 && downsample, divider, d_M, d_H);
 }
 
 

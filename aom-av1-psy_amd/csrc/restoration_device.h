@@ -1,5 +1,6 @@
-// What restoration.hip shares with the restoration composites (sgr_search.hip): the unit clip of its kernels and the launch of the self-guided
-// filter without the entry point's argument checks.  Not part of the ABI.
+// What the restoration files share: the unit clip of restoration.hip's kernels and the launches of its self-guided filter and Wiener statistics
+// without the entry points' argument checks (sgr_search.hip, wiener_search.hip), the workgroup sum of the two searches, and the stripe row rule
+// with the two Wiener passes of the frame filter (lr_frame.hip, wiener_search.hip).  Not part of the ABI.
 #ifndef AOMHIP_CSRC_RESTORATION_DEVICE_H_
 #define AOMHIP_CSRC_RESTORATION_DEVICE_H_
 
@@ -19,6 +20,101 @@ __device__ __forceinline__ aomhip_rect clip_unit(aomhip_rect u, int plane_w, int
 // aomhip_selfguided_restoration_batch's launch on the context's stream (its arguments, already checked; n_units > 0).  restoration.hip
 void launch_selfguided(aomhip_ctx *ctx, const aomhip_planes *dgd, int dgd_frame, const aomhip_rect *d_units, int n_units, const int32_t *d_sgr_params_idx,
                        int max_unit_width, int max_unit_height, int32_t *d_flt0, int32_t *d_flt1, int flt_stride, int64_t flt_pitch);
+
+// av1_compute_stats[_highbd]'s launch (aomhip_compute_stats_batch's arguments, already checked; n_units > 0; dgd / src point at pixel (0, 0) of their
+// frames).  `wide`: the instantiation whose LDS tile takes units up to 384 pixels wide instead of 256.  restoration.hip
+void launch_wiener_stats(hipStream_t stream, int bit_depth, int wiener_win, bool wide, int n_units, const void *dgd, int dgd_stride, const void *src,
+                         int src_stride, const aomhip_rect *d_units, int downsample, int64_t *d_M, int64_t *d_H);
+
+#ifdef __HIPCC__
+// the sum of v over a workgroup of NT lanes, in every lane
+template <int NT> __device__ __forceinline__ long long wg_sum(long long v, long long *scratch /* NT / 64 */) {
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
+  __syncthreads();
+  long long s = 0;
+#pragma unroll
+  for (int k = 0; k < NT / 64; ++k) s += scratch[k];
+  return s;
+}
+
+// ---- the piece of the stripe-exact filters (the comment at the top of lr_frame.hip): 32 rows of one stripe x kLrPW columns, 256 lanes
+#ifndef AOMHIP_LR_PW
+#define AOMHIP_LR_PW 64                                        // 64 or 32 (tools/gpu_lr_frame.py measured both)
+#endif
+constexpr int kLrPW = AOMHIP_LR_PW, kLrPH = 32;                // piece: columns x rows
+static_assert(kLrPW == 64 || kLrPW == 32, "a wavefront covers one or two rows of a piece");
+constexpr int kLrFW = kLrPW + 6, kLrFH = kLrPH + 6;            // its footprint
+constexpr int kLrMaxUnit = 384;                                // RESTORATION_UNITSIZE_MAX * 3 / 2: a last unit is < 1.5 unit sizes
+constexpr int kLrPerLane = kLrPW * kLrPH / 256;                // pixels per lane: one column, rows lr_row(tid, 0 .. kLrPerLane - 1)
+
+// Row q of a lane.  All rows of a WAVEFRONT have one parity (the r[0] filter treats even and odd rows differently: no divergence): 64 columns -- a
+// wavefront is a row, rows wave + 4 q; 32 columns -- a wavefront is two rows two apart, rows 8 q + (wave & 1) + 2 * half + 4 * (wave >> 1).
+__device__ __forceinline__ int lr_row(int tid, int q) {
+  if (kLrPW == 64) return (tid >> 6) + 4 * q;
+  return 8 * q + ((tid >> 6) & 1) + 2 * ((tid >> 5) & 1) + 4 * (tid >> 7);
+}
+
+// The footprint of the piece whose first pixel is (ox, py0), in stripe rows [y0, y1) of the plane: rows py0 - 3 .. py0 + kLrPH + 2 through the ROW RULE,
+// columns ox - 3 .. ox + kLrPW + 2 clamped to the plane, into s_d[kLrFH * kLrFW] by the 256 lanes tid = 0 .. 255 (the caller's barrier follows).
+// (a fixed trip count, unrolled, loads first and LDS stores after: all of a lane's loads are in flight together; rows below a short piece's
+// footprint load a valid row nobody reads)
+template <typename T>
+__device__ __forceinline__ void lr_stage_footprint(uint16_t *s_d, int tid, const T *__restrict__ deb, int deb_stride, const T *__restrict__ cdef,
+                                                   int cdef_stride, int ox, int py0, int y0, int y1, int plane_w, int plane_h) {
+  constexpr int kStage = (kLrFH * kLrFW + 255) / 256;
+  uint16_t staged[kStage];
+#pragma unroll
+  for (int it = 0; it < kStage; ++it) {
+    const int t = min(tid + it * 256, kLrFH * kLrFW - 1);
+    const int fy = t / kLrFW, fx = t - fy * kLrFW;
+    const int y = py0 - 3 + fy, x = min(max(ox - 3 + fx, 0), plane_w - 1);
+    bool from_deb = false;
+    int ry = y;
+    if (y < y0) {
+      from_deb = y0 > 0;
+      ry = from_deb ? max(y, y0 - 2) : 0;
+    } else if (y >= y1) {
+      from_deb = y1 < plane_h;
+      ry = from_deb ? min(y, y1 + 1) : plane_h - 1;
+    }
+    ry = min(max(ry, 0), plane_h - 1);
+    const T *src = from_deb ? deb + (int64_t)ry * deb_stride : cdef + (int64_t)ry * cdef_stride;
+    staged[it] = (uint16_t)src[x];
+  }
+#pragma unroll
+  for (int it = 0; it < kStage; ++it)
+    if (tid + it * 256 < kLrFH * kLrFW) s_d[tid + it * 256] = staged[it];
+}
+
+// av1_[highbd_]wiener_convolve_add_src with get_conv_params_wiener(bd) on a staged piece of ph rows; taps 0 .. 6 (tap 7 of the stored filters is 0,
+// InterpKernel padding), the centre tap stored without its implicit + 128.  The horizontal pass: footprint rows 0 .. ph + 5 into
+// s_tmp[(ph + 6) x kLrPW] (temp row r = footprint row r; the caller's barrier follows) ...
+__device__ __forceinline__ void lr_wiener_hpass(const uint16_t *s_d, uint16_t *s_tmp, int tid, int ph, const int (&fh)[7], int bd) {
+  const int round_0 = bd == 12 ? 5 : 3;
+  const int limit = (1 << (bd + 8 - round_0)) - 1;   // WIENER_CLAMP_LIMIT
+  for (int t = tid; t < kLrFH * kLrPW; t += 256) {
+    const int r = t / kLrPW, x = t & (kLrPW - 1);
+    if (r >= ph + 6) break;
+    const uint16_t *s = s_d + r * kLrFW + x;   // footprint column x = source column x - 3
+    int sum = ((int)s[3] << 7) + (1 << (bd + 6));
+#pragma unroll
+    for (int q = 0; q < 7; ++q) sum += (int)s[q] * fh[q];
+    s_tmp[t] = (uint16_t)min(max((sum + ((1 << round_0) >> 1)) >> round_0, 0), limit);
+  }
+}
+// ... and the vertical pass for the piece's pixel (i, lx): the filtered pixel, clipped to the bit depth
+__device__ __forceinline__ int lr_wiener_vpixel(const uint16_t *s_tmp, int i, int lx, const int (&fv)[7], int bd) {
+  const int round_1 = 14 - (bd == 12 ? 5 : 3);
+  const uint16_t *s = s_tmp + i * kLrPW + lx;   // temp row i = source row i - 3
+  int sum = ((int)s[3 * kLrPW] << 7) - (1 << (bd + round_1 - 1));
+#pragma unroll
+  for (int t = 0; t < 7; ++t) sum += (int)s[t * kLrPW] * fv[t];
+  const int v = (sum + ((1 << round_1) >> 1)) >> round_1;
+  return min(max(v, 0), (1 << bd) - 1);
+}
+#endif  // __HIPCC__
 
 }  // namespace aomhip
 

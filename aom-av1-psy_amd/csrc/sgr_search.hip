@@ -91,17 +91,6 @@ __device__ __forceinline__ int solve_tap(int64_t div, int64_t det) {
   return (int)signed_rounded_divide(div * (1 << kPrjBits), det);
 }
 
-template <int NT> __device__ __forceinline__ long long wg_sum(long long v, long long *scratch /* NT / 64 */) {
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  long long s = 0;
-#pragma unroll
-  for (int k = 0; k < NT / 64; ++k) s += scratch[k];
-  return s;
-}
-
 // The pixels of one list entry as a workgroup of NT lanes walks them: lane t takes pixels t, t + NT, ... in row-major order, (row, column) kept
 // incrementally; the loops are unrolled by 4 so that a wavefront has the loads of four pixels in flight (a large unit's workgroup is alone on its CU).
 template <typename T, int NT> struct UnitPixels {

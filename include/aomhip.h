@@ -1577,6 +1577,50 @@ int aomhip_search_selfguided_restoration_batch(aomhip_ctx *ctx, const aomhip_pla
                                                const aomhip_rect *d_units, const aomhip_rect *h_units, int n_units, int enable_sgr_ep_pruning,
                                                aomhip_sgr_search_result *d_best, aomhip_sgr_search_result *d_per_ep);
 
+/* search_wiener (av1/encoder/pickrst.c:1503-1636) for every restoration unit of a list, on the device from the statistics to the refined filter.  Per
+ * unit, in the reference's order: av1_compute_stats[_highbd] with wiener_win (the reference's reduced_wiener_win: 7, or 5 for chroma and for luma
+ * under reduce_wiener_window_size; use_downsampled_wiener_stats for 8 bits only) on `cdef` and `src`; wiener_decompose_sep_sym (:1250-1280: four rounds
+ * of update_a_sep_sym / update_b_sep_sym with linsolve_wiener); finalize_sym_filter of both filters; compute_score (:1285-1322) -- a score > 0 ends the
+ * unit; finer_tile_search_wiener (:1396-1501) as written, every step of it a try_restoration_unit (:199-224): av1_loop_restoration_filter_unit with
+ * optimized_lr == 0 and the whole-frame tile, i.e. aomhip_loop_restoration_filter_units' stripe row rule with `deblocked` context rows, and the SSE of
+ * the unit against `src`; the filtered pixels never reach memory.  The whole chain is integer arithmetic and is held bit for bit.
+ *   `src`, `deblocked`, `cdef`  three rings of one geometry and bit depth (8, 10 or 12); the plane is width x height of the rings (for chroma pass
+ *                        the chroma rings and ss_y).  cdef: border >= 3, extended as av1_extend_frame leaves it (the statistics read it); src and
+ *                        deblocked need no border.
+ *   d_result[i]          hfilter / vfilter = the WienerInfo rusi->wiener holds after the walk (centre tap without its implicit + 128, tap 7 = 0) or,
+ *                        when score > 0, the finalized filter the score was computed for; sse = rusi->sse[RESTORE_WIENER], INT64_MAX when
+ *                        score > 0 (:1588-1596); sse_none = sse_restoration_unit(cdef, src) = rusi->sse[RESTORE_NONE] (search_norestore :1651), in
+ *                        every case; score = compute_score of the finalized filter; trials = the try_restoration_unit calls made (0 when
+ *                        score > 0); singular = how many of the 8 update_a / update_b calls had linsolve_wiener return 0.
+ *   d_trace[i * AOMHIP_WIENER_MAX_TRIALS + t]  trial t of unit i: taps 0 .. 2 of the horizontal and the vertical filter tried, and its SSE; the first
+ *                        record is the finalized filter; entries past `trials` are left untouched.  May be NULL.  The walk makes at most 75 trials
+ *                        (1 + 2 x 37: tests/test_golden_wiener_search.py derives it from the tap ranges and the walk's structure).
+ * Units up to 384 x 384.  h_units: the same list in host memory for argument checking, or NULL; with it a unit is refused if it is empty, outside
+ * the plane, larger than 384, or has a v_start / v_end that is neither the plane's edge nor a stripe boundary
+ * (aomhip_loop_restoration_filter_units' rule); on the device a unit is clipped to the plane and to 384 x 384.  Stream-ordered on the context's
+ * stream, no host synchronisation: statistics and walk state live in the context's work memory, at most 64 MiB of M / H at a time (3423 units; longer
+ * lists go in chunks); growing the work memory synchronises, so run the call once before capturing it.  An empty list is no error.
+ * prune_wiener_based_on_src_var, count_wiener_bits against rsc->wiener, the RD comparison and skip_sgr_eval read encoder state that chains across
+ * units and stay with the host. */
+#define AOMHIP_WIENER_MAX_TRIALS 96
+typedef struct {
+  int16_t hfilter[8], vfilter[8];
+  int64_t sse;
+  int64_t sse_none;
+  int64_t score;
+  int32_t trials;
+  int32_t singular;
+} aomhip_wiener_search_result;   /* 64 bytes */
+typedef struct {
+  int8_t h[3], v[3];
+  int16_t pad;
+  int64_t err;
+} aomhip_wiener_trial;           /* 16 bytes */
+int aomhip_search_wiener_batch(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *deblocked, int deblocked_frame,
+                               const aomhip_planes *cdef, int cdef_frame, int ss_y, int wiener_win, const aomhip_rect *d_units,
+                               const aomhip_rect *h_units, int n_units, int use_downsampled_wiener_stats, aomhip_wiener_search_result *d_result,
+                               aomhip_wiener_trial *d_trace);
+
 /* ------------------------------------------------------------------ rtcd-signature conformance entry points */
 
 /* aom_dsp_rtcd_defs.pl:762-763 aom_sad{W}x{H} / aom_sad_skip_{W}x{H}; host pointers. */
