@@ -138,6 +138,14 @@ WIENER_MAX_TRIALS = 96
 wiener_search_result_dtype = np.dtype([("hfilter", "<i2", (8,)), ("vfilter", "<i2", (8,)), ("sse", "<i8"), ("sse_none", "<i8"), ("score", "<i8"), ("trials", "<i4"),
                                        ("singular", "<i4")])
 wiener_trial_dtype = np.dtype([("h", "i1", (3,)), ("v", "i1", (3,)), ("pad", "<i2"), ("err", "<i8")])
+# aomhip_lr_pick_params (72 bytes), aomhip_lr_unit_search (88 bytes), aomhip_lr_plane_pick (104 bytes): aomhip_pick_filter_restoration_plane; the plane's
+# costs are doubles, compared as their 64-bit patterns (view "<u8")
+lr_pick_params_dtype = np.dtype([("rdmult", "<i4"), ("wiener_restore_cost", "<i4", (2,)), ("sgrproj_restore_cost", "<i4", (2,)),
+                                 ("switchable_restore_cost", "<i4", (3,)), ("force_restore_type", "<i4"), ("wiener_win", "<i4"), ("reduced_wiener_win", "<i4"),
+                                 ("use_downsampled_wiener_stats", "<i4"), ("enable_sgr_ep_pruning", "<i4"), ("prune_wiener_based_on_src_var", "<i4"),
+                                 ("prune_sgr_based_on_wiener", "<i4"), ("dual_sgr_penalty_level", "<i4"), ("wiener_src_var_thresh", "<u8")])
+lr_unit_search_dtype = np.dtype([("sse", "<i8", (3,)), ("best_rtype", "<i4", (3,)), ("skip_sgr_eval", "<i4"), ("wiener_sgr", lr_unit_info_dtype)])
+lr_plane_pick_dtype = np.dtype([("frame_restoration_type", "<i4"), ("searched", "<i4"), ("cost", "<f8", (4,)), ("bits", "<i8", (4,)), ("sse", "<i8", (4,))])
 scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_qn", "subpel_y_qn", "dst_x", "dst_y")])   # aomhip_scaled_block
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
@@ -290,6 +298,8 @@ _protos = {
     "aomhip_pixel_proj_error_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _vp, _vp, _i, _vp]),
     "aomhip_search_selfguided_restoration_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_search_wiener_batch": (C.c_int, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "aomhip_lr_trial_sse_units": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "aomhip_pick_filter_restoration_plane": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "aomhip_wedge_sse_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "aomhip_wedge_sign_from_residuals_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "aomhip_wedge_compute_delta_squares_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
@@ -964,6 +974,24 @@ class Context:
         hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
         check(lib.aomhip_search_wiener_batch(self.h, C.byref(src), src_frame, C.byref(deblocked), deblocked_frame, C.byref(cdef), cdef_frame, ss_y, wiener_win,
                                              d_units, hu, n_units, downsample, d_result, d_trace), "aomhip_search_wiener_batch")
+
+    def lr_trial_sse_units(self, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, plane_w, plane_h, ss_y, d_units, h_units, n_units, d_info, d_sse):
+        """try_restoration_unit per unit (rect_dtype, lr_unit_info_dtype records): loop_restoration_filter_units, then the unit's SSE against `src` (int64
+        each), without the output ring."""
+        hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
+        check(lib.aomhip_lr_trial_sse_units(self.h, C.byref(src), src_frame, C.byref(deblocked), deblocked_frame, C.byref(cdef), cdef_frame, plane_w, plane_h, ss_y,
+                                            d_units, hu, n_units, d_info, d_sse), "aomhip_lr_trial_sse_units")
+
+    def pick_filter_restoration_plane(self, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, ss_y, d_units, h_units, n_units, params, d_skip_sgr_eval,
+                                      d_search, d_info, d_plane):
+        """The plane loop's body of av1_pick_filter_restoration for one plane: params = one lr_pick_params_dtype record (host), d_skip_sgr_eval = one byte
+        per unit (read and written: zero it before luma, pass it again for U and V), d_search (lr_unit_search_dtype, may be None), d_info (lr_unit_info_dtype,
+        ready for loop_restoration_filter_units), d_plane (one lr_plane_pick_dtype record, may be None)."""
+        hu = None if h_units is None else np.ascontiguousarray(h_units).ctypes.data
+        pp = None if params is None else np.ascontiguousarray(params, lr_pick_params_dtype).ctypes.data
+        check(lib.aomhip_pick_filter_restoration_plane(self.h, C.byref(src), src_frame, C.byref(deblocked), deblocked_frame, C.byref(cdef), cdef_frame, ss_y,
+                                                       d_units, hu, n_units, pp, d_skip_sgr_eval, d_search, d_info, d_plane),
+              "aomhip_pick_filter_restoration_plane")
 
     def scaled_pred_batch(self, ref, ref_frame, pred, pred_frame, bw, bh, fx, fy, x_step_qn, y_step_qn, d_blocks, n_blocks):
         """av1_[highbd_]convolve_2d_scale for a batch of blocks (scaled_block_dtype records), single reference."""

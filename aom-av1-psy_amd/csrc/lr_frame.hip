@@ -32,13 +32,8 @@
 
 namespace aomhip {
 
-#include "sgr_table.inc"
-__device__ const int kLrSgrParams[16][4] = AOMHIP_SGR_PARAMS;
-__device__ const int32_t kLrXByXplus1[256] = AOMHIP_X_BY_XPLUS1;
-__device__ const int32_t kLrOneByX[25] = AOMHIP_ONE_BY_X;
-
-constexpr int kLrAW = kLrPW + 2, kLrAH = kLrPH + 2;            // positions -1 .. 64 x -1 .. 32 of A[] / B[]
-// (the piece, its footprint, the row rule and the two Wiener passes: restoration_device.h, shared with wiener_search.hip)
+// (the piece, its footprint, the row rule, the two Wiener passes and the self-guided pass: restoration_device.h, shared with wiener_search.hip and
+// lr_pick.hip)
 
 template <typename T>
 __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb, int deb_stride, const T *__restrict__ cdef, int cdef_stride,
@@ -74,82 +69,14 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb
   // the footprint: rows py0 - 3 .. py1 + 2 through the row rule, columns ox - 3 .. ox + pw + 2 clamped to the plane
   lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, y0, y1, plane_w, plane_h);
   __syncthreads();
-  const int mx = (1 << bd) - 1;
 
   if (type == 2) {
-    const int idx = info[ui].sgr_params_idx & 15;
-    const int r0 = kLrSgrParams[idx][0], r1 = kLrSgrParams[idx][1];
-    const int xqd0 = info[ui].xqd[0], xqd1 = info[ui].xqd[1];
-    int xq0, xq1;   // av1_decode_xq (:631-643)
-    if (r0 == 0) { xq0 = 0; xq1 = 128 - xqd1; }
-    else if (r1 == 0) { xq0 = xqd0; xq1 = 0; }
-    else { xq0 = xqd0; xq1 = 128 - xq0 - xqd1; }
-    int32_t acc[kLrPerLane];
-#pragma unroll
-    for (int q = 0; q < kLrPerLane; ++q) acc[q] = ((int32_t)s_d[(lr_row(tid, q) + 3) * kLrFW + lx + 3] << 4) << 7;   // u << SGRPROJ_PRJ_BITS
-    const int sh = bd - 8;
-    for (int pass = 0; pass < 2; ++pass) {
-      const int r = pass ? r1 : r0, sv = kLrSgrParams[idx][2 + pass], xq = pass ? xq1 : xq0;
-      if (r <= 0) continue;   // (uniform)
-      const int n = (2 * r + 1) * (2 * r + 1);
-      const uint32_t one_by_x = (uint32_t)kLrOneByX[n - 1];
-      // A, B at piece positions (i, j) in [-1, ph] x [-1, pw]: s_A[(i + 1) * kLrAW + j + 1]; the r[0] filter reads the odd rows only
-      for (int t = tid; t < kLrAH * kLrAW; t += 256) {
-        const int ai = t / kLrAW, aj = t - ai * kLrAW;
-        if (ai > ph + 1 || aj > pw + 1 || (pass == 0 && (ai & 1))) continue;
-        uint32_t sum = 0, sq = 0;
-        for (int y = -r; y <= r; ++y)
-          for (int x = -r; x <= r; ++x) {
-            const uint32_t v = s_d[(ai + 2 + y) * kLrFW + (aj + 2 + x)];   // footprint row of position i is i + 3 = ai + 2
-            sum += v; sq += v * v;
-          }
-        const uint32_t a = (sq + ((1u << (2 * sh)) >> 1)) >> (2 * sh), b = (sum + ((1u << sh) >> 1)) >> sh;
-        const uint32_t pp = (a * n < b * b) ? 0u : a * n - b * b;
-        const uint32_t z = (pp * (uint32_t)sv + (1u << 19)) >> 20;                       // SGRPROJ_MTABLE_BITS
-        const int32_t A = kLrXByXplus1[z < 255u ? z : 255u];
-        s_A[t] = A;
-        s_B[t] = (int32_t)(((uint32_t)(256 - A) * sum * one_by_x + (1u << 11)) >> 12);   // SGRPROJ_SGR, SGRPROJ_RECIP_BITS
-      }
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < kLrPerLane; ++q) {
-        const int i = lr_row(tid, q);   // (its parity is the wavefront's)
-        if (i < ph && lx < pw) {
-          const int c = (i + 1) * kLrAW + (lx + 1);
-          int32_t a, b;
-          int nb;
-          if (pass == 0) {
-            if (!(i & 1)) {
-              nb = 5;
-              a = (s_A[c - kLrAW] + s_A[c + kLrAW]) * 6 + (s_A[c - 1 - kLrAW] + s_A[c - 1 + kLrAW] + s_A[c + 1 - kLrAW] + s_A[c + 1 + kLrAW]) * 5;
-              b = (s_B[c - kLrAW] + s_B[c + kLrAW]) * 6 + (s_B[c - 1 - kLrAW] + s_B[c - 1 + kLrAW] + s_B[c + 1 - kLrAW] + s_B[c + 1 + kLrAW]) * 5;
-            } else {
-              nb = 4;
-              a = s_A[c] * 6 + (s_A[c - 1] + s_A[c + 1]) * 5;
-              b = s_B[c] * 6 + (s_B[c - 1] + s_B[c + 1]) * 5;
-            }
-          } else {
-            nb = 5;
-            a = (s_A[c] + s_A[c - 1] + s_A[c + 1] + s_A[c - kLrAW] + s_A[c + kLrAW]) * 4 +
-                (s_A[c - 1 - kLrAW] + s_A[c - 1 + kLrAW] + s_A[c + 1 - kLrAW] + s_A[c + 1 + kLrAW]) * 3;
-            b = (s_B[c] + s_B[c - 1] + s_B[c + 1] + s_B[c - kLrAW] + s_B[c + kLrAW]) * 4 +
-                (s_B[c - 1 - kLrAW] + s_B[c - 1 + kLrAW] + s_B[c + 1 - kLrAW] + s_B[c + 1 + kLrAW]) * 3;
-          }
-          const int32_t d = s_d[(i + 3) * kLrFW + lx + 3];
-          const int32_t v = a * d + b;
-          const int rs = 8 + nb - 4;   // SGRPROJ_SGR_BITS + nb - SGRPROJ_RST_BITS
-          acc[q] += xq * (((v + ((1 << rs) >> 1)) >> rs) - (d << 4));
-        }
-      }
-      __syncthreads();
-    }
+    int px[kLrPerLane];
+    lr_sgr_piece(s_d, s_A, s_B, tid, ph, pw, info[ui].sgr_params_idx, info[ui].xqd[0], info[ui].xqd[1], bd, px);
 #pragma unroll
     for (int q = 0; q < kLrPerLane; ++q) {
       const int i = lr_row(tid, q);
-      if (i < ph && lx < pw) {
-        const int wv = (int)(int16_t)((acc[q] + (1 << 10)) >> 11);   // (int16_t)ROUND_POWER_OF_TWO(v, SGRPROJ_PRJ_BITS + SGRPROJ_RST_BITS)
-        dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)min(max(wv, 0), mx);
-      }
+      if (i < ph && lx < pw) dst[(int64_t)(py0 + i) * dst_stride + ox + lx] = (T)px[q];
     }
     return;
   }

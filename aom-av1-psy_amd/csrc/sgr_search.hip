@@ -1,8 +1,8 @@
 // libaomhip -- the self-guided restoration search of a list of restoration units as one device pass: search_selfguided_restoration
 // (av1/encoder/pickrst.c:804-863, called by search_sgrproj :882-946) with everything below it -- compute_sgrproj_err (:774-791: apply_sgr, get_proj_subspace
 // :660-731, encode_xq :733-748, finer_search_pixel_proj_error :402-461), get_best_error (:793-802) and both orders over the parameter sets (:818-856 with
-// the seed and group tables of :44-53).  What reads encoder state (count_sgrproj_bits against rsc->sgrproj, the RD comparison, skip_sgr_eval) stays with
-// the host: a chain across units.
+// the seed and group tables of :44-53).  What reads encoder state (count_sgrproj_bits against rsc->sgrproj, the RD comparison, skip_sgr_eval) is a chain
+// across units: lr_pick.hip's, which runs this search through search_selfguided_ws; a host that calls the entry point alone keeps it.
 //
 // Mapping.  The search is a short chain of STAGES, each a fixed number of parameter sets per unit: all 16 without pruning; with it the 4 seeds,
 // the winner's 2 neighbours, one set of group 2 and one of group 3 -- which sets, the stage before decides per unit.  Per stage three launches, no
@@ -251,6 +251,57 @@ static void launch_eval(hipStream_t st, int bd, bool big, int n_ent, const aomhi
   f(st, n_ent, src, so, dat, po, ent_units, ent_ep, count, flt0, flt1, flt_stride, flt_pitch, per_ep);
 }
 
+// the chunk of units whose flt0 / flt1 fit kFltBudget, and the layout of a call's work memory
+struct SgrWork {
+  int32_t *flt0, *flt1, *ent_ep[4], *ent_idx;
+  aomhip_rect *ent_units;
+  aomhip_sgr_search_result *per_ep;
+  int chunk;
+  void layout(WorkCarver &c, int n_units, int max_w, int max_h, const SgrStages &st, bool with_per_ep) {
+    const int64_t flt_pitch = (int64_t)max_w * max_h;
+    chunk = (int)std::min<int64_t>(n_units, std::max<int64_t>(1, (int64_t)(kFltBudget / (2 * sizeof(int32_t))) / (flt_pitch * st.eps[0])));
+    const size_t n_ent = (size_t)chunk * st.eps[0];   // (stage 0 has the most entries)
+    c(flt0, n_ent * flt_pitch); c(flt1, n_ent * flt_pitch);
+    for (int s = 0; s < 4; ++s) c(ent_ep[s], (size_t)chunk * st.eps[s]);
+    c(ent_idx, n_ent); c(ent_units, n_ent);
+    c(per_ep, with_per_ep ? (size_t)n_units * 16 : 0);
+  }
+};
+size_t search_selfguided_bytes(int n_units, int max_w, int max_h, int pruning, bool with_per_ep) {
+  SgrWork w;
+  return carve_bytes([&](WorkCarver &c) { w.layout(c, n_units, max_w, max_h, stages_of(pruning), with_per_ep); });
+}
+
+void search_selfguided_ws(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dat, int dat_frame, const aomhip_rect *d_units,
+                          int n_units, int max_w, int max_h, int pruning, aomhip_sgr_search_result *d_best, aomhip_sgr_search_result *d_per_ep, char *ws) {
+  const int bd = dat->bit_depth;
+  const SgrStages st = stages_of(pruning);
+  const int flt_stride = max_w;
+  const int64_t flt_pitch = (int64_t)flt_stride * max_h;
+  const bool big = flt_pitch > kBigUnitPixels;
+  SgrWork w;
+  WorkCarver carver{ ws };
+  w.layout(carver, n_units, max_w, max_h, st, d_per_ep == nullptr);
+  const int chunk = w.chunk;
+  int32_t *flt0 = w.flt0, *flt1 = w.flt1, **ent_ep = w.ent_ep, *ent_idx = w.ent_idx;
+  aomhip_rect *ent_units = w.ent_units;
+  aomhip_sgr_search_result *per_ep = d_per_ep ? d_per_ep : w.per_ep;
+  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
+  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
+  for (int c0 = 0; c0 < n_units; c0 += chunk) {
+    const int n = min(chunk, n_units - c0);
+    for (int s = 0; s <= st.n; ++s) {   // (the last round only folds the last stage)
+      const int count = s < st.n ? st.eps[s] : 0;
+      hipLaunchKernelGGL(sgr_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, s, pruning, dat->width, dat->height, max_w, max_h,
+                         s > 0 ? ent_ep[s - 1] : nullptr, s > 0 ? st.eps[s - 1] : 0, ent_units, s < st.n ? ent_ep[s] : nullptr, ent_idx, count,
+                         per_ep + 16 * (int64_t)c0, d_best + c0);
+      if (count == 0) break;
+      launch_selfguided(ctx, dat, dat_frame, ent_units, n * count, ent_idx, max_w, max_h, flt0, flt1, flt_stride, flt_pitch);
+      launch_eval(ctx->stream, bd, big, n * count, src, so, dat, po, ent_units, ent_ep[s], count, flt0, flt1, flt_stride, flt_pitch, per_ep + 16 * (int64_t)c0);
+    }
+  }
+}
+
 }  // namespace aomhip
 
 using namespace aomhip;
@@ -285,38 +336,9 @@ extern "C" int aomhip_search_selfguided_restoration_batch(aomhip_ctx *ctx, const
   if (n_units == 0) return AOMHIP_OK;
 
   const int pruning = enable_sgr_ep_pruning != 0;
-  const SgrStages st = stages_of(pruning);
-  const int flt_stride = max_w;
-  const int64_t flt_pitch = (int64_t)flt_stride * max_h;
-  const bool big = flt_pitch > kBigUnitPixels;
-  const int chunk = (int)std::min<int64_t>(n_units, std::max<int64_t>(1, (int64_t)(kFltBudget / (2 * sizeof(int32_t))) / (flt_pitch * st.eps[0])));
-  const size_t n_ent = (size_t)chunk * st.eps[0];   // (stage 0 has the most entries)
-  int32_t *flt0, *flt1, *ent_ep[4], *ent_idx;
-  aomhip_rect *ent_units;
-  aomhip_sgr_search_result *per_ep;
-  if (!carve_work(ctx, [&](WorkCarver &c) {
-        c(flt0, n_ent * flt_pitch); c(flt1, n_ent * flt_pitch);
-        for (int s = 0; s < 4; ++s) c(ent_ep[s], (size_t)chunk * st.eps[s]);
-        c(ent_idx, n_ent); c(ent_units, n_ent);
-        c(per_ep, d_per_ep ? 0 : (size_t)n_units * 16);
-      }))
-    return AOMHIP_ERR_HIP;
-  if (d_per_ep) per_ep = d_per_ep;
-
-  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
-  for (int c0 = 0; c0 < n_units; c0 += chunk) {
-    const int n = min(chunk, n_units - c0);
-    for (int s = 0; s <= st.n; ++s) {   // (the last round only folds the last stage)
-      const int count = s < st.n ? st.eps[s] : 0;
-      hipLaunchKernelGGL(sgr_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, s, pruning, dat->width, dat->height, max_w, max_h,
-                         s > 0 ? ent_ep[s - 1] : nullptr, s > 0 ? st.eps[s - 1] : 0, ent_units, s < st.n ? ent_ep[s] : nullptr, ent_idx, count,
-                         per_ep + 16 * (int64_t)c0, d_best + c0);
-      if (count == 0) break;
-      launch_selfguided(ctx, dat, dat_frame, ent_units, n * count, ent_idx, max_w, max_h, flt0, flt1, flt_stride, flt_pitch);
-      launch_eval(ctx->stream, bd, big, n * count, src, so, dat, po, ent_units, ent_ep[s], count, flt0, flt1, flt_stride, flt_pitch, per_ep + 16 * (int64_t)c0);
-    }
-  }
+  char *ws;
+  if (!carve_work(ctx, [&](WorkCarver &c) { c(ws, search_selfguided_bytes(n_units, max_w, max_h, pruning, d_per_ep == nullptr)); })) return AOMHIP_ERR_HIP;
+  search_selfguided_ws(ctx, src, src_frame, dat, dat_frame, d_units, n_units, max_w, max_h, pruning, d_best, d_per_ep, ws);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

@@ -2,7 +2,8 @@
 // the statistics to the refined filter -- av1_compute_stats[_highbd], wiener_decompose_sep_sym (:1250-1280) with update_a_sep_sym / update_b_sep_sym
 // (:1132-1248) and linsolve_wiener (:1089-1129), finalize_sym_filter (:1324-1355), compute_score (:1285-1322) and finer_tile_search_wiener
 // (:1396-1501), every step of which is a try_restoration_unit (:199-224).  What reads encoder state (prune_wiener_based_on_src_var,
-// count_wiener_bits against rsc->wiener, the RD comparison, skip_sgr_eval) stays with the host: a chain across units.  All of it is integer arithmetic.
+// count_wiener_bits against rsc->wiener, the RD comparison, skip_sgr_eval) is a chain across units: lr_pick.hip's, which runs this search through
+// search_wiener_ws; a host that calls the entry point alone keeps it.  All of it is integer arithmetic.
 //
 // Mapping.  Per chunk of units four launches, no host round trip between them:
 //   wiener_prep_kernel    one lane per unit: the unit clipped to the plane and to 384 x 384 (identity for every list the entry point accepts)
@@ -385,6 +386,48 @@ static void launch_walk_t(hipStream_t st, int n, const aomhip_planes *src, int64
                      cdef->width, cdef->height, ss_y, win, res, trace);
 }
 
+// the chunk of units whose M / H fit kStatsBudget, and the layout of a call's work memory
+static int wiener_chunk(int n_units, int wiener_win) {
+  const int win2 = wiener_win * wiener_win;
+  const size_t per_unit = (size_t)(win2 + win2 * win2) * sizeof(int64_t);
+  return (int)std::min<size_t>((size_t)n_units, std::max<size_t>(1, kStatsBudget / per_unit));
+}
+struct WienerWork {
+  int64_t *M, *H;
+  aomhip_rect *clipped;
+  void layout(WorkCarver &c, int chunk, int win2) { c(M, (size_t)chunk * win2); c(H, (size_t)chunk * win2 * win2); c(clipped, (size_t)chunk); }
+};
+size_t search_wiener_bytes(int n_units, int wiener_win) {
+  WienerWork w;
+  return carve_bytes([&](WorkCarver &c) { w.layout(c, wiener_chunk(n_units, wiener_win), wiener_win * wiener_win); });
+}
+
+void search_wiener_ws(aomhip_ctx *ctx, const aomhip_planes *src, int64_t so, const aomhip_planes *deblocked, int64_t eo, const aomhip_planes *cdef,
+                      int64_t co, int ss_y, int wiener_win, const aomhip_rect *d_units, int n_units, bool big, int use_downsampled_wiener_stats,
+                      aomhip_wiener_search_result *d_result, aomhip_wiener_trial *d_trace, char *ws) {
+  const int bd = cdef->bit_depth, plane_w = cdef->width, plane_h = cdef->height;
+  const int chunk = wiener_chunk(n_units, wiener_win);
+  WienerWork w;
+  WorkCarver carver{ ws };
+  w.layout(carver, chunk, wiener_win * wiener_win);
+  int64_t *M = w.M, *H = w.H;
+  aomhip_rect *clipped = w.clipped;
+  const size_t esz = bd == 8 ? 1 : 2;
+  auto walk = bd == 8 ? (big ? launch_walk_t<uint8_t, 1024> : launch_walk_t<uint8_t, 256>) : (big ? launch_walk_t<uint16_t, 1024> : launch_walk_t<uint16_t, 256>);
+  for (int c0 = 0; c0 < n_units; c0 += chunk) {
+    const int n = min(chunk, n_units - c0);
+    hipLaunchKernelGGL(wiener_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, plane_w, plane_h, clipped);
+    launch_wiener_stats(ctx->stream, bd, wiener_win, true, n, static_cast<const char *>(cdef->base) + co * esz, cdef->stride,
+                        static_cast<const char *>(src->base) + so * esz, src->stride, clipped, use_downsampled_wiener_stats != 0, M, H);
+    if (wiener_win == 7)
+      hipLaunchKernelGGL(wiener_solve_kernel<7>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
+    else
+      hipLaunchKernelGGL(wiener_solve_kernel<5>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
+    walk(ctx->stream, n, src, so, deblocked, eo, cdef, co, clipped, ss_y, wiener_win, d_result + c0,
+         d_trace ? d_trace + (int64_t)c0 * AOMHIP_WIENER_MAX_TRIALS : nullptr);
+  }
+}
+
 }  // namespace aomhip
 
 using namespace aomhip;
@@ -432,34 +475,12 @@ extern "C" int aomhip_search_wiener_batch(aomhip_ctx *ctx, const aomhip_planes *
   }
   if (n_units == 0) return AOMHIP_OK;
 
-  const int win2 = wiener_win * wiener_win;
-  const size_t per_unit = (size_t)(win2 + win2 * win2) * sizeof(int64_t);
-  const int chunk = (int)std::min<size_t>((size_t)n_units, std::max<size_t>(1, kStatsBudget / per_unit));
-  int64_t *M, *H;
-  aomhip_rect *clipped;
-  if (!carve_work(ctx, [&](WorkCarver &c) {
-        c(M, (size_t)chunk * win2); c(H, (size_t)chunk * win2 * win2);
-        c(clipped, (size_t)chunk);
-      }))
-    return AOMHIP_ERR_HIP;
-
-  const size_t esz = bd == 8 ? 1 : 2;
+  char *ws;
+  if (!carve_work(ctx, [&](WorkCarver &c) { c(ws, search_wiener_bytes(n_units, wiener_win)); })) return AOMHIP_ERR_HIP;
   const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
   const int64_t eo = (int64_t)deblocked_frame * deblocked->frame_stride + (int64_t)deblocked->border * deblocked->stride + deblocked->border;
   const int64_t co = (int64_t)cdef_frame * cdef->frame_stride + (int64_t)cdef->border * cdef->stride + cdef->border;
-  auto walk = bd == 8 ? (big ? launch_walk_t<uint8_t, 1024> : launch_walk_t<uint8_t, 256>) : (big ? launch_walk_t<uint16_t, 1024> : launch_walk_t<uint16_t, 256>);
-  for (int c0 = 0; c0 < n_units; c0 += chunk) {
-    const int n = min(chunk, n_units - c0);
-    hipLaunchKernelGGL(wiener_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, plane_w, plane_h, clipped);
-    launch_wiener_stats(ctx->stream, bd, wiener_win, true, n, static_cast<const char *>(cdef->base) + co * esz, cdef->stride,
-                        static_cast<const char *>(src->base) + so * esz, src->stride, clipped, use_downsampled_wiener_stats != 0, M, H);
-    if (wiener_win == 7)
-      hipLaunchKernelGGL(wiener_solve_kernel<7>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
-    else
-      hipLaunchKernelGGL(wiener_solve_kernel<5>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
-    walk(ctx->stream, n, src, so, deblocked, eo, cdef, co, clipped, ss_y, wiener_win, d_result + c0,
-         d_trace ? d_trace + (int64_t)c0 * AOMHIP_WIENER_MAX_TRIALS : nullptr);
-  }
+  search_wiener_ws(ctx, src, so, deblocked, eo, cdef, co, ss_y, wiener_win, d_units, n_units, big, use_downsampled_wiener_stats, d_result, d_trace, ws);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

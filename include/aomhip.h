@@ -1568,7 +1568,8 @@ int aomhip_pixel_proj_error_batch(aomhip_ctx *ctx, const aomhip_planes *src, int
  * Stream-ordered on the context's stream, no host synchronisation (the filter outputs live in the context's work memory, at most 512 MiB of them at
  * a time; growing it synchronises, so run the call once before capturing it).  h_units: the same list in host memory for argument checking and for
  * sizing the scratch rows to the largest unit, or NULL (384 x 384 is then assumed; on the device a unit is clipped to the plane and to that size).
- * count_sgrproj_bits, the RD comparison and skip_sgr_eval read encoder state and stay with the host. */
+ * count_sgrproj_bits, the RD comparison and skip_sgr_eval read encoder state that chains across units: aomhip_pick_filter_restoration_plane runs them
+ * on the device around this search; a host that calls this entry point alone keeps them. */
 typedef struct {
   int32_t ep, xqd[2], visited;
   int64_t err;
@@ -1601,7 +1602,7 @@ int aomhip_search_selfguided_restoration_batch(aomhip_ctx *ctx, const aomhip_pla
  * stream, no host synchronisation: statistics and walk state live in the context's work memory, at most 64 MiB of M / H at a time (3423 units; longer
  * lists go in chunks); growing the work memory synchronises, so run the call once before capturing it.  An empty list is no error.
  * prune_wiener_based_on_src_var, count_wiener_bits against rsc->wiener, the RD comparison and skip_sgr_eval read encoder state that chains across
- * units and stay with the host. */
+ * units: aomhip_pick_filter_restoration_plane runs them on the device around this search; a host that calls this entry point alone keeps them. */
 #define AOMHIP_WIENER_MAX_TRIALS 96
 typedef struct {
   int16_t hfilter[8], vfilter[8];
@@ -1620,6 +1621,76 @@ int aomhip_search_wiener_batch(aomhip_ctx *ctx, const aomhip_planes *src, int sr
                                const aomhip_planes *cdef, int cdef_frame, int ss_y, int wiener_win, const aomhip_rect *d_units,
                                const aomhip_rect *h_units, int n_units, int use_downsampled_wiener_stats, aomhip_wiener_search_result *d_result,
                                aomhip_wiener_trial *d_trace);
+
+/* try_restoration_unit (av1/encoder/pickrst.c:199-224) for every unit of a list, each with its own RestorationUnitInfo -- Wiener, self-guided or none:
+ * av1_loop_restoration_filter_unit with optimized_lr == 0 and the whole-frame tile, then sse_restoration_unit (:85-92) of the unit against `src`.  It is
+ * aomhip_loop_restoration_filter_units followed by the units' SSE, without the output ring: the restored pixels never reach memory.  `src` has the
+ * geometry and bit depth of the other two rings; everything else, the argument checks included, is that call's.  d_sse[i] = the unit's SSE (int64).
+ * One workgroup per (unit, piece) writes a partial sum into the context's work memory and a second launch adds a unit's partial sums up: stream-ordered,
+ * no host synchronisation, no atomics (growing the work memory synchronises, so run the call once before capturing it). */
+int aomhip_lr_trial_sse_units(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *deblocked, int deblocked_frame,
+                              const aomhip_planes *cdef, int cdef_frame, int plane_w, int plane_h, int ss_y, const aomhip_rect *d_units,
+                              const aomhip_rect *h_units, int n_units, const aomhip_lr_unit_info *d_info, int64_t *d_sse);
+
+/* The body of the plane loop of av1_pick_filter_restoration (av1/encoder/pickrst.c:1751-1838, the loop :1794-1835) for ONE plane whose restoration is not
+ * disabled, as one stream-ordered call: search_rest_type (:1732-1744) for RESTORE_NONE, RESTORE_WIENER, RESTORE_SGRPROJ and RESTORE_SWITCHABLE in turn
+ * -- search_norestore (:1638-1655), search_wiener (:1503-1636: the variance prune of its head through var_restoration_unit -> aom_var_2d_u8_c /
+ * aom_var_2d_u16_c, aom_dsp/sum_squares.c:42-73, aomhip_search_wiener_batch's chain on the units that survive, count_wiener_bits :1357-1393 against
+ * rsc->wiener, the RD comparison and skip_sgr_eval of its tail), search_sgrproj (:882-946: aomhip_search_selfguided_restoration_batch's chain on the
+ * units whose skip_sgr_eval is 0, try_restoration_unit of the winner, count_sgrproj_bits :865-880 against rsc->sgrproj, the dual-filter penalty and the
+ * RD comparison), search_switchable (:1657-1719) -- then the plane's frame_restoration_type (:1812-1826) and copy_unit_info (:1721-1730).  The bit
+ * counts are aom_count_primitive_refsubexpfin's (aom_dsp/binary_codes_writer.c:84-129, aom_dsp/recenter.h:40-59); the costs are
+ * RDCOST_DBL_WITH_NATIVE_BD_DIST (av1/encoder/rd.h:39-41) in IEEE doubles, each operation rounded on its own, equal to the host's bit for bit.
+ *   rings, ss_y       as for aomhip_search_wiener_batch: three rings of one geometry and bit depth, the plane is the rings' width x height; cdef: border
+ *                     >= 3, extended as av1_extend_frame leaves it (:1808-1810).
+ *   d_units           aomhip_lr_units_in_plane's list in unit_idx order: the order of the three chains (rsc->wiener, rsc->sgrproj, both in
+ *                     search_switchable).  n_units == 1 drops RESTORE_SWITCHABLE as num_rtypes does (:1799-1800).  h_units: the same list in host memory
+ *                     for argument checking (both searches' rules) and for sizing the scratch rows, or NULL.
+ *   params            see aomhip_lr_pick_params.  force_restore_type: get_forced_restore_types (:104-111) -- 4 (RESTORE_TYPES) searches everything, 1 or 2
+ *                     only that type and RESTORE_NONE (the fork's AOM_CONTENT_PSY forces 2: the Wiener search then does not run and
+ *                     sse[RESTORE_NONE] is sse_restoration_unit's alone).
+ *   d_skip_sgr_eval   one uint8_t per unit, READ AND WRITTEN: rusi->skip_sgr_eval.  The reference allocates rusi once and reuses it for the three planes
+ *                     (:1765-1775), and under prune_sgr_based_on_wiener == 1 a unit that leaves search_wiener through the variance prune or through
+ *                     compute_score > 0 keeps the flag the same index had in the plane before.  So the caller zeroes the array once before luma and
+ *                     passes the same array again for U and V.
+ *   d_search[i]       RestUnitSearchInfo of unit i after all searches of the plane.  sse[r] is INT64_MAX where the reference sets that, 0 (the memset
+ *                     of :1775) where search r did not run; best_rtype[r - 1] is -1 where search r did not run; wiener_sgr holds rusi->wiener where
+ *                     search_wiener assigned it and rusi->sgrproj where search_sgrproj assigned it, 0 elsewhere (the reference keeps stale values of
+ *                     the plane before there and never reads them); its restoration_type is 0.  May be NULL.
+ *   d_info[i]         what copy_unit_info leaves for the winning frame type, ready for aomhip_loop_restoration_filter_units: restoration_type =
+ *                     best_rtype[frame type - 1] with that type's fields, the other type's fields 0.  Frame type RESTORE_NONE: every unit type 0.
+ *   d_plane           the plane's record, see aomhip_lr_plane_pick.  May be NULL.
+ * Stream-ordered on the context's stream; no host synchronisation once the work memory exists (growing it synchronises: run the call once before
+ * capturing it).  Refused: what the two searches refuse, force_restore_type outside { 1, 2, 4 }, pruning levels outside 0 .. 2, windows other than
+ * 7 / 5, a negative dual_sgr_penalty_level.  Out of scope, as for the frame filter: superres, optimized_lr, and disable_loop_restoration_luma / _chroma
+ * -- for the last the caller does not call. */
+typedef struct {
+  int32_t rdmult;                        /* x->rdmult = cpi->rd.RDMULT (:1776) */
+  int32_t wiener_restore_cost[2], sgrproj_restore_cost[2], switchable_restore_cost[3];   /* x->mode_costs, av1_fill_lr_rates (:1758) */
+  int32_t force_restore_type;            /* get_forced_restore_types: 4 (RESTORE_TYPES) = all, 1 or 2 = that type and RESTORE_NONE only */
+  int32_t wiener_win, reduced_wiener_win;/* 7 / 5 as search_wiener derives them for the plane (:1542-1549): count_wiener_bits / the statistics */
+  int32_t use_downsampled_wiener_stats, enable_sgr_ep_pruning;
+  int32_t prune_wiener_based_on_src_var; /* 0, 1, 2 */
+  int32_t prune_sgr_based_on_wiener;     /* 0, 1, 2 */
+  int32_t dual_sgr_penalty_level;
+  uint64_t wiener_src_var_thresh;        /* (qs * qs * scale[level]) >> 4 of :1518-1525; the host has av1_dc_quant_QTX */
+} aomhip_lr_pick_params;      /* 72 bytes */
+typedef struct {            /* RestUnitSearchInfo (:113-128) after all searches of the plane */
+  int64_t sse[3];           /* NONE, WIENER, SGRPROJ; INT64_MAX as the reference sets it */
+  int32_t best_rtype[3];    /* for frame type WIENER, SGRPROJ, SWITCHABLE; -1 where that search did not run */
+  int32_t skip_sgr_eval;
+  aomhip_lr_unit_info wiener_sgr;   /* rusi->wiener and rusi->sgrproj (restoration_type unused) */
+} aomhip_lr_unit_search;      /* 88 bytes */
+typedef struct {
+  int32_t frame_restoration_type;   /* cm->rst_info[plane].frame_restoration_type (:1826) */
+  int32_t searched;                 /* bit r set: search_rest_type(r) ran */
+  double  cost[4];                  /* its return value (:1742-1743); 0 where it did not run */
+  int64_t bits[4], sse[4];          /* rsc->bits, rsc->sse at its end */
+} aomhip_lr_plane_pick;       /* 104 bytes */
+int aomhip_pick_filter_restoration_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *deblocked, int deblocked_frame,
+                                         const aomhip_planes *cdef, int cdef_frame, int ss_y, const aomhip_rect *d_units, const aomhip_rect *h_units,
+                                         int n_units, const aomhip_lr_pick_params *params, uint8_t *d_skip_sgr_eval, aomhip_lr_unit_search *d_search,
+                                         aomhip_lr_unit_info *d_info, aomhip_lr_plane_pick *d_plane);
 
 /* ------------------------------------------------------------------ rtcd-signature conformance entry points */
 
