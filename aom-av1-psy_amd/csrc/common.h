@@ -111,6 +111,19 @@ inline PlaneView<T> view_of(const aomhip_planes &p) {
   return v;
 }
 
+// element offset of pixel (0, 0) of a frame in its ring, and that pixel's address for one element type
+inline int64_t frame_origin(const aomhip_planes *p, int frame) { return (int64_t)frame * p->frame_stride + (int64_t)p->border * p->stride + p->border; }
+template <typename T>
+inline T *pixels(const aomhip_planes *p, int frame) {
+  return static_cast<T *>(p->base) + frame_origin(p, frame);
+}
+// f(uint8_t{}) for 8-bit planes, f(uint16_t{}) for deeper ones; returns what f returns (tx_size.h's with_tx_size, for the pixel type)
+template <typename F>
+auto with_pixel(int bit_depth, F &&f) {
+  if (bit_depth == 8) return f(uint8_t{});
+  return f(uint16_t{});
+}
+
 // one frame of a ring as a ring of one (the batched searches pair src / ref by frame index)
 inline aomhip_planes one_frame(const aomhip_planes &p, int f) {
   aomhip_planes v = p;

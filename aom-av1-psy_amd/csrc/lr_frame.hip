@@ -32,8 +32,8 @@
 
 namespace aomhip {
 
-// (the piece, its footprint, the row rule, the two Wiener passes and the self-guided pass: restoration_device.h, shared with wiener_search.hip and
-// lr_pick.hip)
+// (the piece, its place in a unit, its footprint, the row rule, the two Wiener passes and the self-guided pass: restoration_device.h, shared with
+// wiener_search.hip and lr_pick.hip)
 
 template <typename T>
 __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb, int deb_stride, const T *__restrict__ cdef, int cdef_stride,
@@ -43,17 +43,10 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb
   __shared__ uint16_t s_d[kLrFH * kLrFW];
   __shared__ int32_t s_A[kLrAH * kLrAW], s_B[kLrAH * kLrAW];
   const int tid = threadIdx.x, ui = blockIdx.x;
-  aomhip_rect u = units[ui];   // clipped to the plane and to the largest unit there is: identity for every list the entry point accepts
-  u.h_start = min(max(u.h_start, 0), plane_w); u.v_start = min(max(u.v_start, 0), plane_h);
-  u.h_end = min(min(u.h_end, plane_w), u.h_start + kLrMaxUnit); u.v_end = min(min(u.v_end, plane_h), u.v_start + kLrMaxUnit);
-  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
-  const int p = blockIdx.y / tiles_x, tx = blockIdx.y - p * tiles_x;
-  const int ox = u.h_start + tx * kLrPW;                         // first column of the tile
-  const int k = (u.v_start + off) / SH + p / pps;                // the stripe
-  const int y0 = max(max(0, k * SH - off), u.v_start), y1 = min(min((k + 1) * SH - off, plane_h), u.v_end);
-  const int py0 = y0 + (p % pps) * kLrPH, py1 = min(py0 + kLrPH, y1);
-  if (ox >= u.h_end || py0 >= py1) return;
-  const int pw = min(kLrPW, u.h_end - ox), ph = py1 - py0;
+  const aomhip_rect u = clip_unit(units[ui], plane_w, plane_h, kLrMaxUnit, kLrMaxUnit);   // identity for every list the entry point accepts
+  const LrPiece pc = lr_piece_of(u, blockIdx.y, tiles_x, ss_y, plane_h);
+  if (pc.empty) return;
+  const int ox = pc.ox, py0 = pc.py0, pw = pc.pw, ph = pc.ph;
   const int type = info[ui].restoration_type;
 
   const int lx = tid & (kLrPW - 1);
@@ -66,8 +59,8 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const T *__restrict__ deb
     return;
   }
 
-  // the footprint: rows py0 - 3 .. py1 + 2 through the row rule, columns ox - 3 .. ox + pw + 2 clamped to the plane
-  lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, y0, y1, plane_w, plane_h);
+  // the footprint: rows py0 - 3 .. py0 + ph + 2 through the row rule, columns ox - 3 .. ox + pw + 2 clamped to the plane
+  lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, pc.y0, pc.y1, plane_w, plane_h);
   __syncthreads();
 
   if (type == 2) {
@@ -110,55 +103,21 @@ extern "C" int aomhip_loop_restoration_filter_units(aomhip_ctx *ctx, const aomhi
     set_error("%s: invalid argument", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int bd = cdef->bit_depth;
-  if ((bd != 8 && bd != 10 && bd != 12) || deblocked->bit_depth != bd || dst->bit_depth != bd) {
-    set_error("%s: the three rings differ in bit depth (%d / %d / %d; 8, 10 or 12)", who, deblocked->bit_depth, bd, dst->bit_depth);
-    return AOMHIP_ERR_INVALID;
-  }
-  if (deblocked->width != cdef->width || deblocked->height != cdef->height || dst->width != cdef->width || dst->height != cdef->height ||
-      plane_w > cdef->width || plane_h > cdef->height) {
-    set_error("%s: the three rings differ in geometry, or the %d x %d crop area does not fit their %d x %d", who, plane_w, plane_h, cdef->width,
-              cdef->height);
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!check_rings(who, { cdef, deblocked, dst }, plane_w, plane_h)) return AOMHIP_ERR_INVALID;
   if ((dst->base == cdef->base && dst_frame == cdef_frame) || (dst->base == deblocked->base && dst_frame == deblocked_frame)) {
     set_error("%s: dst is one of the inputs (the filter is out of place)", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
-  int max_w = kLrMaxUnit, max_stripes = (kLrMaxUnit + SH - 1) / SH + 1;
-  if (h_units) {
-    max_w = 1; max_stripes = 1;
-    for (int i = 0; i < n_units; ++i) {
-      const aomhip_rect &r = h_units[i];
-      if (r.h_start < 0 || r.v_start < 0 || r.h_end > plane_w || r.v_end > plane_h || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-          r.h_end - r.h_start > kLrMaxUnit || r.v_end - r.v_start > kLrMaxUnit) {
-        set_error("%s: unit %d is empty, outside the %d x %d plane or larger than %d", who, i, plane_w, plane_h, kLrMaxUnit);
-        return AOMHIP_ERR_INVALID;
-      }
-      if ((r.v_end != plane_h && (r.v_end + off) % SH != 0) || (r.v_start != 0 && (r.v_start + off) % SH != 0)) {
-        set_error("%s: unit %d covers rows %d .. %d: a unit starts at row 0 or a stripe boundary k * %d - %d and ends at one or at the plane's bottom", who, i,
-                  r.v_start, r.v_end, SH, off);
-        return AOMHIP_ERR_INVALID;
-      }
-      max_w = max(max_w, r.h_end - r.h_start);
-      max_stripes = max(max_stripes, (r.v_end - 1 + off) / SH - (r.v_start + off) / SH + 1);
-    }
-  }
+  UnitListExtent ext;
+  if (!check_unit_list(who, h_units, n_units, plane_w, plane_h, kLrMaxUnit, kLrMaxUnit, &ext, ss_y)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
-  const int tiles_x = (max_w + kLrPW - 1) / kLrPW;
-  const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * max_stripes * pps));
-  const int64_t eo = (int64_t)deblocked_frame * deblocked->frame_stride + (int64_t)deblocked->border * deblocked->stride + deblocked->border;
-  const int64_t co = (int64_t)cdef_frame * cdef->frame_stride + (int64_t)cdef->border * cdef->stride + cdef->border;
-  const int64_t qo = (int64_t)dst_frame * dst->frame_stride + (int64_t)dst->border * dst->stride + dst->border;
-  if (bd == 8)
-    hipLaunchKernelGGL(lr_frame_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(deblocked->base) + eo, deblocked->stride,
-                       static_cast<const uint8_t *>(cdef->base) + co, cdef->stride, static_cast<uint8_t *>(dst->base) + qo, dst->stride, d_units, d_info,
-                       8, plane_w, plane_h, ss_y, tiles_x);
-  else
-    hipLaunchKernelGGL(lr_frame_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(deblocked->base) + eo,
-                       deblocked->stride, static_cast<const uint16_t *>(cdef->base) + co, cdef->stride, static_cast<uint16_t *>(dst->base) + qo,
-                       dst->stride, d_units, d_info, bd, plane_w, plane_h, ss_y, tiles_x);
+  const int tiles_x = (ext.w + kLrPW - 1) / kLrPW, pps = (64 >> ss_y) / kLrPH;
+  const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * ext.stripes * pps));
+  with_pixel(cdef->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(lr_frame_kernel<T>, grid, dim3(256), 0, ctx->stream, pixels<T>(deblocked, deblocked_frame), deblocked->stride, pixels<T>(cdef, cdef_frame),
+                       cdef->stride, pixels<T>(dst, dst_frame), dst->stride, d_units, d_info, cdef->bit_depth, plane_w, plane_h, ss_y, tiles_x);
+  });
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

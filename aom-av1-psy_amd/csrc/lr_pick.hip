@@ -60,15 +60,10 @@ __global__ __launch_bounds__(256) void lr_trial_kernel(const T *__restrict__ src
   __shared__ long long scratch[4];
   const int tid = threadIdx.x, ui = blockIdx.x, lx = tid & (kLrPW - 1);
   const aomhip_rect u = clip_unit(units[ui], plane_w, plane_h, kLrMaxUnit, kLrMaxUnit);
-  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
-  const int p = blockIdx.y / tiles_x, tx = blockIdx.y - p * tiles_x;
-  const int ox = u.h_start + tx * kLrPW;
-  const int k = (u.v_start + off) / SH + p / pps;
-  const int y0 = max(max(0, k * SH - off), u.v_start), y1 = min(min((k + 1) * SH - off, plane_h), u.v_end);
-  const int py0 = y0 + (p % pps) * kLrPH, py1 = min(py0 + kLrPH, y1);
+  const LrPiece pc = lr_piece_of(u, blockIdx.y, tiles_x, ss_y, plane_h);
   long long err = 0;
-  if (ox < u.h_end && py0 < py1) {   // (uniform over the workgroup, like everything below but the bounds of a lane's pixels)
-    const int pw = min(kLrPW, u.h_end - ox), ph = py1 - py0;
+  if (!pc.empty) {   // (uniform over the workgroup, like everything below but the bounds of a lane's pixels)
+    const int ox = pc.ox, py0 = pc.py0, pw = pc.pw, ph = pc.ph;
     const int type = info[ui].restoration_type;
     // the source pixels of this lane first, from addresses clamped into the piece: their latency hides behind the filter
     int sv[kLrPerLane], px[kLrPerLane];
@@ -78,7 +73,7 @@ __global__ __launch_bounds__(256) void lr_trial_kernel(const T *__restrict__ src
 #pragma unroll
       for (int q = 0; q < kLrPerLane; ++q) px[q] = (int)cdef[(int64_t)(py0 + min(lr_row(tid, q), ph - 1)) * cdef_stride + min(ox + lx, u.h_end - 1)];
     } else {
-      lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, y0, y1, plane_w, plane_h);
+      lr_stage_footprint(s_d, tid, deb, deb_stride, cdef, cdef_stride, ox, py0, pc.y0, pc.y1, plane_w, plane_h);
       __syncthreads();
       if (type == 2) {
         lr_sgr_piece(s_d, s_A, s_B, tid, ph, pw, info[ui].sgr_params_idx, info[ui].xqd[0], info[ui].xqd[1], bd, px);
@@ -116,21 +111,17 @@ __global__ __launch_bounds__(256) void lr_trial_reduce_kernel(const long long *_
 // the grid's second dimension for units up to max_w wide that touch up to max_stripes stripes
 static int trial_pieces(int max_w, int max_stripes, int ss_y) { return (max_w + kLrPW - 1) / kLrPW * max_stripes * ((64 >> ss_y) / kLrPH); }
 
-// both launches (partial: n_units * trial_pieces(..) sums of work memory); so / eo / co: element offsets of pixel (0, 0) of the frame in its ring
-static void launch_trial(hipStream_t st, const aomhip_planes *src, int64_t so, const aomhip_planes *deb, int64_t eo, const aomhip_planes *cdef, int64_t co,
-                         int plane_w, int plane_h, int ss_y, const aomhip_rect *d_units, int n_units, int max_w, int max_stripes,
+// both launches (partial: n_units * trial_pieces(..) sums of work memory)
+static void launch_trial(hipStream_t st, const aomhip_planes *src, int src_frame, const aomhip_planes *deb, int deb_frame, const aomhip_planes *cdef,
+                         int cdef_frame, int plane_w, int plane_h, int ss_y, const aomhip_rect *d_units, int n_units, int max_w, int max_stripes,
                          const aomhip_lr_unit_info *d_info, long long *partial, int64_t *d_sse) {
   const int tiles_x = (max_w + kLrPW - 1) / kLrPW, pieces = trial_pieces(max_w, max_stripes, ss_y);
   const dim3 grid((unsigned)n_units, (unsigned)pieces);
-  const int bd = cdef->bit_depth;
-  if (bd == 8)
-    hipLaunchKernelGGL(lr_trial_kernel<uint8_t>, grid, dim3(256), 0, st, static_cast<const uint8_t *>(src->base) + so, src->stride,
-                       static_cast<const uint8_t *>(deb->base) + eo, deb->stride, static_cast<const uint8_t *>(cdef->base) + co, cdef->stride, d_units, d_info, 8,
-                       plane_w, plane_h, ss_y, tiles_x, partial);
-  else
-    hipLaunchKernelGGL(lr_trial_kernel<uint16_t>, grid, dim3(256), 0, st, static_cast<const uint16_t *>(src->base) + so, src->stride,
-                       static_cast<const uint16_t *>(deb->base) + eo, deb->stride, static_cast<const uint16_t *>(cdef->base) + co, cdef->stride, d_units, d_info,
-                       bd, plane_w, plane_h, ss_y, tiles_x, partial);
+  with_pixel(cdef->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(lr_trial_kernel<T>, grid, dim3(256), 0, st, pixels<T>(src, src_frame), src->stride, pixels<T>(deb, deb_frame), deb->stride,
+                       pixels<T>(cdef, cdef_frame), cdef->stride, d_units, d_info, cdef->bit_depth, plane_w, plane_h, ss_y, tiles_x, partial);
+  });
   hipLaunchKernelGGL(lr_trial_reduce_kernel, dim3((n_units + 255) / 256), dim3(256), 0, st, partial, n_units, pieces, d_sse);
 }
 
@@ -233,8 +224,8 @@ __device__ __forceinline__ int count_wiener_bits(const uint8_t *s_tab, int win, 
 // count_sgrproj_bits (:865-880): SGRPROJ_PARAMS_BITS, then xqd[p] where the set's radius p is on (SGRPROJ_PRJ_MIN0 .. MAX1: n = 128, SGRPROJ_PRJ_SUBEXP_K = 4)
 __device__ __forceinline__ int count_sgrproj_bits(const uint8_t *s_tab, int ep, int x0, int x1, int r0, int r1) {
   int bits = 4;
-  if (kLrSgrParams[ep & 15][0] > 0) bits += count_primitive_refsubexpfin(s_tab, 3, r0 + 96, x0 + 96);
-  if (kLrSgrParams[ep & 15][1] > 0) bits += count_primitive_refsubexpfin(s_tab, 3, r1 + 32, x1 + 32);
+  if (kSgrParams[ep & 15][0] > 0) bits += count_primitive_refsubexpfin(s_tab, 3, r0 + 96, x0 + 96);
+  if (kSgrParams[ep & 15][1] > 0) bits += count_primitive_refsubexpfin(s_tab, 3, r1 + 32, x1 + 32);
   return bits;
 }
 
@@ -473,31 +464,6 @@ __global__ __launch_bounds__(64) void pick_decide_kernel(int n, aomhip_lr_pick_p
   if (lane == 0) *plane = pl;
 }
 
-// the rules both searches and the frame filter apply to a host copy of the list -> false with the error set; also the largest unit
-static bool check_host_units(const char *who, const aomhip_rect *h_units, int n_units, int plane_w, int plane_h, int ss_y, int *max_w, int *max_h,
-                             int *max_stripes) {
-  const int SH = 64 >> ss_y, off = 8 >> ss_y;
-  *max_w = 1; *max_h = 1; *max_stripes = 1;
-  for (int i = 0; i < n_units; ++i) {
-    const aomhip_rect &r = h_units[i];
-    if (r.h_start < 0 || r.v_start < 0 || r.h_end > plane_w || r.v_end > plane_h || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-        r.h_end - r.h_start > kLrMaxUnit || r.v_end - r.v_start > kLrMaxUnit) {
-      set_error("%s: unit %d is empty, outside the %d x %d plane or larger than %d", who, i, plane_w, plane_h, kLrMaxUnit);
-      return false;
-    }
-    if ((r.v_end != plane_h && (r.v_end + off) % SH != 0) || (r.v_start != 0 && (r.v_start + off) % SH != 0)) {
-      set_error("%s: unit %d covers rows %d .. %d: a unit starts at row 0 or a stripe boundary k * %d - %d and ends at one or at the plane's bottom", who, i,
-                r.v_start, r.v_end, SH, off);
-      return false;
-    }
-    *max_w = std::max(*max_w, r.h_end - r.h_start); *max_h = std::max(*max_h, r.v_end - r.v_start);
-    *max_stripes = std::max(*max_stripes, (r.v_end - 1 + off) / SH - (r.v_start + off) / SH + 1);
-  }
-  return true;
-}
-
-static int64_t frame_origin(const aomhip_planes *p, int frame) { return (int64_t)frame * p->frame_stride + (int64_t)p->border * p->stride + p->border; }
-
 }  // namespace aomhip
 
 using namespace aomhip;
@@ -512,25 +478,15 @@ extern "C" int aomhip_lr_trial_sse_units(aomhip_ctx *ctx, const aomhip_planes *s
     set_error("%s: invalid argument", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int bd = cdef->bit_depth;
-  if ((bd != 8 && bd != 10 && bd != 12) || deblocked->bit_depth != bd || src->bit_depth != bd) {
-    set_error("%s: the three rings differ in bit depth (%d / %d / %d; 8, 10 or 12)", who, src->bit_depth, deblocked->bit_depth, bd);
+  UnitListExtent ext;
+  if (!check_rings(who, { cdef, src, deblocked }, plane_w, plane_h) ||
+      !check_unit_list(who, h_units, n_units, plane_w, plane_h, kLrMaxUnit, kLrMaxUnit, &ext, ss_y))
     return AOMHIP_ERR_INVALID;
-  }
-  if (deblocked->width != cdef->width || deblocked->height != cdef->height || src->width != cdef->width || src->height != cdef->height ||
-      plane_w > cdef->width || plane_h > cdef->height) {
-    set_error("%s: the three rings differ in geometry, or the %d x %d crop area does not fit their %d x %d", who, plane_w, plane_h, cdef->width,
-              cdef->height);
-    return AOMHIP_ERR_INVALID;
-  }
-  const int SH = 64 >> ss_y;
-  int max_w = kLrMaxUnit, max_h = kLrMaxUnit, max_stripes = (kLrMaxUnit + SH - 1) / SH + 1;
-  if (h_units && !check_host_units(who, h_units, n_units, plane_w, plane_h, ss_y, &max_w, &max_h, &max_stripes)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
   long long *partial;
-  if (!carve_work(ctx, [&](WorkCarver &c) { c(partial, (size_t)n_units * trial_pieces(max_w, max_stripes, ss_y)); })) return AOMHIP_ERR_HIP;
-  launch_trial(ctx->stream, src, frame_origin(src, src_frame), deblocked, frame_origin(deblocked, deblocked_frame), cdef, frame_origin(cdef, cdef_frame), plane_w,
-               plane_h, ss_y, d_units, n_units, max_w, max_stripes, d_info, partial, d_sse);
+  if (!carve_work(ctx, [&](WorkCarver &c) { c(partial, (size_t)n_units * trial_pieces(ext.w, ext.stripes, ss_y)); })) return AOMHIP_ERR_HIP;
+  launch_trial(ctx->stream, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, plane_w, plane_h, ss_y, d_units, n_units, ext.w, ext.stripes, d_info,
+               partial, d_sse);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -555,21 +511,17 @@ extern "C" int aomhip_pick_filter_restoration_plane(aomhip_ctx *ctx, const aomhi
               P.dual_sgr_penalty_level);
     return AOMHIP_ERR_INVALID;
   }
+  if (!check_rings(who, { cdef, src, deblocked })) return AOMHIP_ERR_INVALID;
   const int bd = cdef->bit_depth;
-  if ((bd != 8 && bd != 10 && bd != 12) || src->bit_depth != bd || deblocked->bit_depth != bd || src->width != cdef->width || src->height != cdef->height ||
-      deblocked->width != cdef->width || deblocked->height != cdef->height) {
-    set_error("%s: the three rings differ in bit depth (%d / %d / %d; 8, 10 or 12) or geometry", who, src->bit_depth, deblocked->bit_depth, bd);
-    return AOMHIP_ERR_INVALID;
-  }
   if (P.use_downsampled_wiener_stats && bd != 8) {
     set_error("%s: the down-sampled statistics exist for 8 bits only", who);
     return AOMHIP_ERR_INVALID;
   }
   const int plane_w = cdef->width, plane_h = cdef->height;
-  const int SH = 64 >> ss_y;
-  int max_w = kLrMaxUnit, max_h = kLrMaxUnit, max_stripes = (kLrMaxUnit + SH - 1) / SH + 1;
-  if (h_units && !check_host_units(who, h_units, n_units, plane_w, plane_h, ss_y, &max_w, &max_h, &max_stripes)) return AOMHIP_ERR_INVALID;
+  UnitListExtent ext;
+  if (!check_unit_list(who, h_units, n_units, plane_w, plane_h, kLrMaxUnit, kLrMaxUnit, &ext, ss_y)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
+  const int max_w = ext.w, max_h = ext.h, max_stripes = ext.stripes;
 
   const bool run_wiener = P.force_restore_type == kRestoreTypes || P.force_restore_type == 1;
   const bool run_sgr = P.force_restore_type == kRestoreTypes || P.force_restore_type == 2;
@@ -600,24 +552,22 @@ extern "C" int aomhip_pick_filter_restoration_plane(aomhip_ctx *ctx, const aomhi
   if (d_search) us = d_search;
   if (d_plane) plane = d_plane;
 
-  const int64_t so = frame_origin(src, src_frame), eo = frame_origin(deblocked, deblocked_frame), co = frame_origin(cdef, cdef_frame);
   hipStream_t st = ctx->stream;
-  if (bd == 8)
-    hipLaunchKernelGGL(pick_prep_kernel<uint8_t>, dim3(n_units), dim3(256), 0, st, static_cast<const uint8_t *>(src->base) + so, src->stride,
-                       static_cast<const uint8_t *>(cdef->base) + co, cdef->stride, d_units, plane_w, plane_h, run_wiener ? P.prune_wiener_based_on_src_var : 0,
-                       P.wiener_src_var_thresh, units_c, mask_w, prep);
-  else
-    hipLaunchKernelGGL(pick_prep_kernel<uint16_t>, dim3(n_units), dim3(256), 0, st, static_cast<const uint16_t *>(src->base) + so, src->stride,
-                       static_cast<const uint16_t *>(cdef->base) + co, cdef->stride, d_units, plane_w, plane_h, run_wiener ? P.prune_wiener_based_on_src_var : 0,
-                       P.wiener_src_var_thresh, units_c, mask_w, prep);
+  with_pixel(bd, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(pick_prep_kernel<T>, dim3(n_units), dim3(256), 0, st, pixels<T>(src, src_frame), src->stride, pixels<T>(cdef, cdef_frame), cdef->stride,
+                       d_units, plane_w, plane_h, run_wiener ? P.prune_wiener_based_on_src_var : 0, P.wiener_src_var_thresh, units_c, mask_w, prep);
+  });
   if (run_wiener)
-    search_wiener_ws(ctx, src, so, deblocked, eo, cdef, co, ss_y, P.reduced_wiener_win, mask_w, n_units, big, P.use_downsampled_wiener_stats, wres, nullptr, sub);
+    search_wiener_ws(ctx, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, ss_y, P.reduced_wiener_win, mask_w, n_units, big,
+                     P.use_downsampled_wiener_stats, wres, nullptr, sub);
   hipLaunchKernelGGL(pick_wiener_chain_kernel, dim3(1), dim3(64), 0, st, n_units, P, bd, run_wiener ? 1 : 0, units_c, prep, wres, d_skip_sgr_eval, us, mask_s,
                      plane);
   if (run_sgr) {
     search_selfguided_ws(ctx, src, src_frame, cdef, cdef_frame, mask_s, n_units, max_w, max_h, pruning, sbest, nullptr, sub);
     hipLaunchKernelGGL(pick_sgr_info_kernel, dim3((n_units + 255) / 256), dim3(256), 0, st, n_units, sbest, tinfo);
-    launch_trial(st, src, so, deblocked, eo, cdef, co, plane_w, plane_h, ss_y, mask_s, n_units, max_w, max_stripes, tinfo, partial, sgr_sse);
+    launch_trial(st, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, plane_w, plane_h, ss_y, mask_s, n_units, max_w, max_stripes, tinfo, partial,
+                 sgr_sse);
   }
   hipLaunchKernelGGL(pick_decide_kernel, dim3(1), dim3(64), 0, st, n_units, P, bd, run_wiener ? 1 : 0, run_sgr ? 1 : 0, run_sw ? 1 : 0, sbest, sgr_sse, us, d_info,
                      plane);

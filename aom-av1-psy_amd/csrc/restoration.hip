@@ -23,8 +23,8 @@
 namespace aomhip {
 
 constexpr int kBandRows = 16;
-constexpr int kMaxUnit = 256;                      // restoration units are at most 256 pixels wide (RESTORATION_UNITSIZE_MAX) ...
-constexpr int kMaxUnitWide = 384;                  // ... but for the last one of a row, up to 1.5 of them: the Wiener search's instantiation (wiener_search.hip)
+constexpr int kMaxUnit = 256;                      // restoration units are at most 256 pixels wide (RESTORATION_UNITSIZE_MAX), but for the last one of a
+                                                   // row: up to kLrMaxUnit, the Wiener search's instantiation (wiener_search.hip)
 
 // MAXW: the widest unit.  The 32-bit band sums hold for 384 too: 4095^2 x 16 rows x 6 column chunks < 2^31.
 template <typename T, int WIN, int MAXW = kMaxUnit>
@@ -158,23 +158,24 @@ __global__ __launch_bounds__(256) void wiener_stats_kernel(const T *__restrict__
   }
 }
 
-template <typename T, int MAXW = kMaxUnit>
-static void launch_stats(hipStream_t st, int win, int n_units, const void *d, int dstride, const void *s, int sstride, const aomhip_rect *units,
-                         int downsample, int divider, int64_t *M, int64_t *H) {
+template <typename T, int MAXW>
+static void launch_stats(hipStream_t st, int win, int n_units, const T *d, int dstride, const T *s, int sstride, const aomhip_rect *units, int downsample,
+                         int divider, int64_t *M, int64_t *H) {
   if (win == 7)
-    hipLaunchKernelGGL((wiener_stats_kernel<T, 7, MAXW>), dim3(n_units * 9), dim3(256), 0, st, static_cast<const T *>(d), dstride,
-                       static_cast<const T *>(s), sstride, units, downsample, divider, M, H);
+    hipLaunchKernelGGL((wiener_stats_kernel<T, 7, MAXW>), dim3(n_units * 9), dim3(256), 0, st, d, dstride, s, sstride, units, downsample, divider, M, H);
   else
-    hipLaunchKernelGGL((wiener_stats_kernel<T, 5, MAXW>), dim3(n_units * 5), dim3(256), 0, st, static_cast<const T *>(d), dstride,
-                       static_cast<const T *>(s), sstride, units, downsample, divider, M, H);
+    hipLaunchKernelGGL((wiener_stats_kernel<T, 5, MAXW>), dim3(n_units * 5), dim3(256), 0, st, d, dstride, s, sstride, units, downsample, divider, M, H);
 }
 
-void launch_wiener_stats(hipStream_t stream, int bit_depth, int wiener_win, bool wide, int n_units, const void *dgd, int dgd_stride, const void *src,
-                         int src_stride, const aomhip_rect *d_units, int downsample, int64_t *d_M, int64_t *d_H) {
-  const int divider = bit_depth == 12 ? 16 : bit_depth == 10 ? 4 : 1;
-  auto f = bit_depth == 8 ? (wide ? launch_stats<uint8_t, kMaxUnitWide> : launch_stats<uint8_t>)
-                          : (wide ? launch_stats<uint16_t, kMaxUnitWide> : launch_stats<uint16_t>);
-  f(stream, wiener_win, n_units, dgd, dgd_stride, src, src_stride, d_units, bit_depth == 8 && downsample, divider, d_M, d_H);
+void launch_wiener_stats(hipStream_t stream, int wiener_win, bool wide, int n_units, const aomhip_planes *dgd, int dgd_frame, const aomhip_planes *src,
+                         int src_frame, const aomhip_rect *d_units, int downsample, int64_t *d_M, int64_t *d_H) {
+  const int bd = dgd->bit_depth, divider = bd == 12 ? 16 : bd == 10 ? 4 : 1;
+  with_pixel(bd, [&](auto px) {
+    using T = decltype(px);
+    auto f = wide ? launch_stats<T, kLrMaxUnit> : launch_stats<T, kMaxUnit>;
+    f(stream, wiener_win, n_units, pixels<T>(dgd, dgd_frame), dgd->stride, pixels<T>(src, src_frame), src->stride, d_units, bd == 8 && downsample, divider, d_M,
+      d_H);
+  });
 }
 
 
@@ -184,11 +185,7 @@ void launch_wiener_stats(hipStream_t stream, int bit_depth, int wiener_win, bool
 // truncated only where they are never used (tests/test_golden_sgr.py checks that property), so a unit's output does not depend on how it is cut: one 256-lane workgroup
 // per 32 x 32 tile of a unit (tile rows start on even rows of the unit: the r[0] filter's row parity), the tile's 38 x 38 footprint staged in LDS
 // once for both filters, A[] / B[] of the 34 x 34 positions the tile's outputs read in LDS, then the weighted 3 x 3 sums.
-#include "sgr_table.inc"
-__device__ const int kSgrParams[16][4] = AOMHIP_SGR_PARAMS;
-__device__ const int32_t kXByXplus1[256] = AOMHIP_X_BY_XPLUS1;
-__device__ const int32_t kOneByX[25] = AOMHIP_ONE_BY_X;
-
+// (the tables and the arithmetic at one position: restoration_device.h, shared with the stripe-exact filters)
 constexpr int kSgrTile = 32, kSgrFoot = kSgrTile + 6, kSgrAB = kSgrTile + 2;
 
 template <typename T>
@@ -212,63 +209,29 @@ __global__ __launch_bounds__(256) void selfguided_kernel(const T *__restrict__ d
     s_d[t] = (int32_t)dgd[(int64_t)(u.v_start + y) * dgd_stride + u.h_start + x];
   }
   __syncthreads();
-  const int sh = bit_depth - 8;
   for (int pass = 0; pass < 2; ++pass) {
     const int r = kSgrParams[idx][pass], sv = kSgrParams[idx][2 + pass];
     if (r <= 0) continue;   // (uniform)
     int32_t *dst = (pass ? flt1 : flt0) + (int64_t)ui * flt_pitch;
-    const int n = (2 * r + 1) * (2 * r + 1);
     // A, B at tile positions (i, j) in [-1, 32]: s_A[(i + 1) * 34 + j + 1]; the r[0] filter needs the odd rows only
     for (int t = threadIdx.x; t < kSgrAB * kSgrAB; t += 256) {
       const int ai = t / kSgrAB, aj = t - ai * kSgrAB;   // position (ai - 1, aj - 1)
       if (pass == 0 && (ai & 1)) continue;                // (ai - 1 even: not computed, not read)
-      uint32_t sum = 0, sq = 0;
-      for (int y = -r; y <= r; ++y)
-        for (int x = -r; x <= r; ++x) {
-          const uint32_t v = (uint32_t)s_d[(ai + 2 + y) * kSgrFoot + (aj + 2 + x)];   // footprint row of position i is i + 3 = ai + 2
-          sum += v; sq += v * v;
-        }
-      const uint32_t a = (sq + ((1u << (2 * sh)) >> 1)) >> (2 * sh), b = (sum + ((1u << sh) >> 1)) >> sh;
-      const uint32_t p = (a * n < b * b) ? 0u : a * n - b * b;
-      const uint32_t z = (p * (uint32_t)sv + (1u << 19)) >> 20;                        // SGRPROJ_MTABLE_BITS
-      const int32_t A = kXByXplus1[z < 255u ? z : 255u];
-      s_A[t] = A;
-      s_B[t] = (int32_t)(((uint32_t)(256 - A) * sum * (uint32_t)kOneByX[n - 1] + (1u << 11)) >> 12);   // SGRPROJ_SGR, SGRPROJ_RECIP_BITS
+      sgr_box_ab<int32_t, kSgrFoot>(s_d + (ai + 2) * kSgrFoot + aj + 2, r, sv, bit_depth - 8, s_A[t], s_B[t]);   // footprint row of position i is i + 3 = ai + 2
     }
     __syncthreads();
     for (int t = threadIdx.x; t < kSgrTile * kSgrTile; t += 256) {
       const int i = t >> 5, j = t & 31;
       if (oy + i >= h || ox + j >= w) continue;
-      const int k = (i + 1) * kSgrAB + (j + 1);
-      int32_t a, b;
-      int nb;
-      if (pass == 0) {
-        if (!(i & 1)) {   // (the tile starts on an even row of the unit)
-          nb = 5;
-          a = (s_A[k - kSgrAB] + s_A[k + kSgrAB]) * 6 + (s_A[k - 1 - kSgrAB] + s_A[k - 1 + kSgrAB] + s_A[k + 1 - kSgrAB] + s_A[k + 1 + kSgrAB]) * 5;
-          b = (s_B[k - kSgrAB] + s_B[k + kSgrAB]) * 6 + (s_B[k - 1 - kSgrAB] + s_B[k - 1 + kSgrAB] + s_B[k + 1 - kSgrAB] + s_B[k + 1 + kSgrAB]) * 5;
-        } else {
-          nb = 4;
-          a = s_A[k] * 6 + (s_A[k - 1] + s_A[k + 1]) * 5;
-          b = s_B[k] * 6 + (s_B[k - 1] + s_B[k + 1]) * 5;
-        }
-      } else {
-        nb = 5;
-        a = (s_A[k] + s_A[k - 1] + s_A[k + 1] + s_A[k - kSgrAB] + s_A[k + kSgrAB]) * 4 +
-            (s_A[k - 1 - kSgrAB] + s_A[k - 1 + kSgrAB] + s_A[k + 1 - kSgrAB] + s_A[k + 1 + kSgrAB]) * 3;
-        b = (s_B[k] + s_B[k - 1] + s_B[k + 1] + s_B[k - kSgrAB] + s_B[k + kSgrAB]) * 4 +
-            (s_B[k - 1 - kSgrAB] + s_B[k - 1 + kSgrAB] + s_B[k + 1 - kSgrAB] + s_B[k + 1 + kSgrAB]) * 3;
-      }
-      const int32_t v = a * s_d[(i + 3) * kSgrFoot + (j + 3)] + b;
-      const int rs = 8 + nb - 4;   // SGRPROJ_SGR_BITS + nb - SGRPROJ_RST_BITS
-      dst[(int64_t)(oy + i) * flt_stride + ox + j] = (v + ((1 << rs) >> 1)) >> rs;
+      const int k = (i + 1) * kSgrAB + j + 1;   // (the tile starts on an even row of the unit: i's parity is the row's)
+      dst[(int64_t)(oy + i) * flt_stride + ox + j] = sgr_filtered<kSgrAB>(s_A + k, s_B + k, pass, i & 1, s_d[(i + 3) * kSgrFoot + j + 3]);
     }
     __syncthreads();
   }
 }
 
-// av1_apply_selfguided_restoration (restoration.c:917-956) after selfguided_kernel: per pixel u = dat << 4, v = (u << 7) + xq0 (flt0 - u) + xq1 (flt1 - u)
-// over the radii in use, (xq0, xq1) = av1_decode_xq(xqd) (:631-643), w = (int16_t)ROUND_POWER_OF_TWO(v, 11), clipped.  One lane per pixel.
+// av1_apply_selfguided_restoration (restoration.c:917-956) after selfguided_kernel: per pixel the projection (restoration_device.h) with (xq0, xq1) =
+// av1_decode_xq(xqd), clipped.  One lane per pixel.
 template <typename T>
 __global__ __launch_bounds__(256) void selfguided_apply_kernel(const T *__restrict__ dat, int dat_stride, T *__restrict__ dst, int dst_stride,
                                                                 const aomhip_rect *__restrict__ units, const int32_t *__restrict__ sgr_idx,
@@ -281,26 +244,21 @@ __global__ __launch_bounds__(256) void selfguided_apply_kernel(const T *__restri
   const int idx = sgr_idx[ui];
   const int r0 = kSgrParams[idx][0], r1 = kSgrParams[idx][1];
   int xq0, xq1;
-  if (r0 == 0) { xq0 = 0; xq1 = 128 - xqd[2 * ui + 1]; }
-  else if (r1 == 0) { xq0 = xqd[2 * ui]; xq1 = 0; }
-  else { xq0 = xqd[2 * ui]; xq1 = 128 - xq0 - xqd[2 * ui + 1]; }
+  sgr_decode_xq(r0, r1, xqd[2 * ui], xqd[2 * ui + 1], xq0, xq1);
   const int32_t *f0 = flt0 + (int64_t)ui * flt_pitch, *f1 = flt1 + (int64_t)ui * flt_pitch;
   const int mx = (1 << bit_depth) - 1;
   for (int t = blockIdx.y * 256 + threadIdx.x; t < w * h; t += gridDim.y * 256) {
     const int i = t / w, j = t - i * w;
     const int uu = (int)dat[(int64_t)(u.v_start + i) * dat_stride + u.h_start + j] << 4;
-    int v = uu << 7;
-    if (r0 > 0) v += xq0 * (f0[(int64_t)i * flt_stride + j] - uu);
-    if (r1 > 0) v += xq1 * (f1[(int64_t)i * flt_stride + j] - uu);
-    const int wv = (int)(int16_t)((v + (1 << 10)) >> 11);
+    const int64_t fo = (int64_t)i * flt_stride + j;
+    const int wv = (int)(int16_t)sgr_proj_round((uu << 7) + sgr_proj_terms(uu, r0, r1, xq0, xq1, f0 + fo, f1 + fo));
     dst[(int64_t)(u.v_start + i) * dst_stride + u.h_start + j] = (T)min(max(wv, 0), mx);
   }
 }
 
 // av1_[highbd_]wiener_convolve_add_src (av1/common/convolve.c:1093-1257) as wiener_filter_stripe calls it (steps of 16): the unit's two 7-tap
-// filters (8 stored taps, centre reduced by 128: the passes add the source back).  One workgroup per 32 x 32 tile: footprint rows -3 .. +4 and
-// columns -3 .. +4 staged in LDS, horizontal pass (+ src << 7 + offset, rounded by round_0, clamped to WIENER_CLAMP_LIMIT) into 40 x 32 uint16,
-// vertical pass (offset removed, rounded by round_1, clipped).  round_0 / round_1 = get_conv_params_wiener(bd): 3 / 11, at 12 bits 5 / 9.
+// filters, all 8 stored taps (the C function multiplies tap 7 whatever it holds).  One workgroup per 32 x 32 tile: footprint rows -3 .. +4 and
+// columns -3 .. +4 staged in LDS, horizontal pass into 40 x 32 uint16, vertical pass from there (the two passes per pixel: restoration_device.h).
 constexpr int kWienerTile = 32, kWienerFoot = kWienerTile + 8;
 template <typename T>
 __global__ __launch_bounds__(256) void wiener_kernel(const T *__restrict__ dat, int dat_stride, T *__restrict__ dst, int dst_stride,
@@ -323,26 +281,16 @@ __global__ __launch_bounds__(256) void wiener_kernel(const T *__restrict__ dat, 
     s_src[t] = (uint16_t)dat[(int64_t)(u.v_start + y) * dat_stride + u.h_start + x];
   }
   __syncthreads();
-  const int round_0 = bd == 12 ? 5 : 3, round_1 = 14 - round_0;
-  const int limit = (1 << (bd + 8 - round_0)) - 1;
   for (int t = threadIdx.x; t < kWienerFoot * kWienerTile; t += 256) {   // temp row r = footprint row r, columns of the tile
     const int r = t >> 5, x = t & 31;
-    const uint16_t *p = s_src + r * kWienerFoot + x;   // footprint column x = source column x - 3
-    int sum = ((int)p[3] << 7) + (1 << (bd + 6));
-#pragma unroll
-    for (int k = 0; k < 8; ++k) sum += (int)p[k] * fx[k];
-    s_tmp[t] = (uint16_t)min(max((sum + ((1 << round_0) >> 1)) >> round_0, 0), limit);
+    s_tmp[t] = wiener_hpixel<8>(s_src + r * kWienerFoot + x, fx, bd);   // footprint column x = source column x - 3
   }
   __syncthreads();
   for (int t = threadIdx.x; t < kWienerTile * kWienerTile; t += 256) {
     const int y = t >> 5, x = t & 31;
     if (oy + y >= h || ox + x >= w) continue;
-    const uint16_t *p = s_tmp + y * kWienerTile + x;   // temp row y = source row y - 3
-    int sum = ((int)p[3 * kWienerTile] << 7) - (1 << (bd + round_1 - 1));
-#pragma unroll
-    for (int k = 0; k < 8; ++k) sum += (int)p[k * kWienerTile] * fy[k];
-    const int v = (sum + ((1 << round_1) >> 1)) >> round_1;
-    dst[(int64_t)(u.v_start + oy + y) * dst_stride + u.h_start + ox + x] = (T)min(max(v, 0), (1 << bd) - 1);
+    // temp row y = source row y - 3
+    dst[(int64_t)(u.v_start + oy + y) * dst_stride + u.h_start + ox + x] = (T)wiener_vpixel<8, kWienerTile>(s_tmp + y * kWienerTile + x, fy, bd);
   }
 }
 
@@ -350,15 +298,6 @@ __global__ __launch_bounds__(256) void wiener_kernel(const T *__restrict__ dat, 
 // get_proj_subspace) and av1_[lowbd|highbd]_pixel_proj_error (:226-370: get_pixel_proj_error, evaluated once per xq that finer_search tries).
 // One 256-lane workgroup per (unit [, xq]): lanes stride the unit's pixels row-major, the sums are exact 64-bit integers (products of
 // two ~17-bit values, up to 2^16 pixels), reduced by shuffles and one LDS step.  Streaming: 2 pixels + 2 int32 per pixel.
-__device__ __forceinline__ long long wg_sum_i64(long long v, long long *scratch /* 4 */) {
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
-  const int wave = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[wave] = v;
-  __syncthreads();
-  return scratch[0] + scratch[1] + scratch[2] + scratch[3];
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void proj_params_kernel(const T *__restrict__ src, int src_stride, const T *__restrict__ dat, int dat_stride,
                                                            const aomhip_rect *__restrict__ units, const int32_t *__restrict__ flt0, const int32_t *__restrict__ flt1,
@@ -380,8 +319,8 @@ __global__ __launch_bounds__(256) void proj_params_kernel(const T *__restrict__ 
     h00 += (long long)a * a; h11 += (long long)b * b; h01 += (long long)a * b;
     c0 += (long long)a * sv; c1 += (long long)b * sv;
   }
-  h00 = wg_sum_i64(h00, scratch); h01 = wg_sum_i64(h01, scratch); h11 = wg_sum_i64(h11, scratch);
-  c0 = wg_sum_i64(c0, scratch); c1 = wg_sum_i64(c1, scratch);
+  h00 = wg_sum<256>(h00, scratch); h01 = wg_sum<256>(h01, scratch); h11 = wg_sum<256>(h11, scratch);
+  c0 = wg_sum<256>(c0, scratch); c1 = wg_sum<256>(c1, scratch);
   if (threadIdx.x == 0) {
     const long long size = n;   // (C's integer division: towards zero, as `H[0][0] /= size` in the reference)
     int64_t *Ho = H + 4 * (int64_t)ui, *Co = C + 2 * (int64_t)ui;
@@ -408,27 +347,23 @@ __global__ __launch_bounds__(256) void proj_error_kernel(const T *__restrict__ s
     const int i = t / w, j = t - i * w;
     const int d = (int)dat[(int64_t)(u.v_start + i) * dat_stride + u.h_start + j], sv = (int)src[(int64_t)(u.v_start + i) * src_stride + u.h_start + j];
     const int uu = d << 4;
-    int v = 1 << 10;                                     // half of 1 << (SGRPROJ_RST_BITS + SGRPROJ_PRJ_BITS)
-    if (r0 > 0) v += xq0 * (f0[(int64_t)i * flt_stride + j] - uu);
-    if (r1 > 0) v += xq1 * (f1[(int64_t)i * flt_stride + j] - uu);
-    const int e = ((r0 > 0 || r1 > 0) ? (v >> 11) : 0) + d - sv;
+    const int64_t fo = (int64_t)i * flt_stride + j;
+    const int e = sgr_proj_round(sgr_proj_terms(uu, r0, r1, xq0, xq1, f0 + fo, f1 + fo)) + d - sv;
     err += (long long)e * e;
   }
-  err = wg_sum_i64(err, scratch);
+  err = wg_sum<256>(err, scratch);
   if (threadIdx.x == 0) err_out[(int64_t)ui * n_xq + qi] = err;
 }
 
 void launch_selfguided(aomhip_ctx *ctx, const aomhip_planes *dgd, int dgd_frame, const aomhip_rect *d_units, int n_units, const int32_t *d_sgr_params_idx,
                        int max_unit_width, int max_unit_height, int32_t *d_flt0, int32_t *d_flt1, int flt_stride, int64_t flt_pitch) {
   const int tiles_x = (max_unit_width + kSgrTile - 1) / kSgrTile, tiles_y = (max_unit_height + kSgrTile - 1) / kSgrTile;
-  const int64_t po = (int64_t)dgd_frame * dgd->frame_stride + (int64_t)dgd->border * dgd->stride + dgd->border;
   const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * tiles_y));
-  if (dgd->bit_depth == 8)
-    hipLaunchKernelGGL(selfguided_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(dgd->base) + po, dgd->stride, d_units,
-                       d_sgr_params_idx, 8, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
-  else
-    hipLaunchKernelGGL(selfguided_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(dgd->base) + po, dgd->stride, d_units,
-                       d_sgr_params_idx, dgd->bit_depth, d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
+  with_pixel(dgd->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(selfguided_kernel<T>, grid, dim3(256), 0, ctx->stream, pixels<T>(dgd, dgd_frame), dgd->stride, d_units, d_sgr_params_idx, dgd->bit_depth,
+                       d_flt0, d_flt1, flt_stride, flt_pitch, tiles_x, dgd->width, dgd->height, max_unit_width, max_unit_height);
+  });
 }
 
 }  // namespace aomhip
@@ -445,25 +380,9 @@ extern "C" int aomhip_compute_stats_batch(aomhip_ctx *ctx, const aomhip_planes *
     set_error("aomhip_compute_stats_batch: invalid argument (window 7 or 5; border >= 3; the down-sampled mode exists for 8-bit only)");
     return AOMHIP_ERR_INVALID;
   }
-  for (int i = 0; h_units && i < n_units; ++i) {
-    const aomhip_rect &r = h_units[i];
-    if (r.h_start < 0 || r.v_start < 0 || r.h_end > dgd->width || r.v_end > dgd->height || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-        r.h_end - r.h_start > kMaxUnit) {
-      set_error("aomhip_compute_stats_batch: unit %d is empty, outside the plane or wider than %d", i, kMaxUnit);
-      return AOMHIP_ERR_INVALID;
-    }
-  }
+  if (!check_unit_list("aomhip_compute_stats_batch", h_units, n_units, dgd->width, dgd->height, kMaxUnit, INT_MAX)) return AOMHIP_ERR_INVALID;   // (any height)
   if (n_units == 0) return AOMHIP_OK;
-  const size_t esz = dgd->bit_depth == 8 ? 1 : 2;
-  const char *d = static_cast<const char *>(dgd->base) +
-                  ((size_t)dgd_frame * dgd->frame_stride + (size_t)dgd->border * dgd->stride + dgd->border) * esz;
-  const char *s = static_cast<const char *>(src->base) +
-                  ((size_t)src_frame * src->frame_stride + (size_t)src->border * src->stride + src->border) * esz;
-  const int divider = dgd->bit_depth == 12 ? 16 : dgd->bit_depth == 10 ? 4 : 1;
-  if (esz == 1)
-    launch_stats<uint8_t>(ctx->stream, wiener_win, n_units, d, dgd->stride, s, src->stride, d_units, use_downsampled_wiener_stats != 0, divider, d_M, d_H);
-  else
-    launch_stats<uint16_t>(ctx->stream, wiener_win, n_units, d, dgd->stride, s, src->stride, d_units, 0, divider, d_M, d_H);
+  launch_wiener_stats(ctx->stream, wiener_win, false, n_units, dgd, dgd_frame, src, src_frame, d_units, use_downsampled_wiener_stats != 0, d_M, d_H);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -485,14 +404,11 @@ extern "C" int aomhip_calc_proj_params_batch(aomhip_ctx *ctx, const aomhip_plane
   if (rc != AOMHIP_OK) return rc;
   if (n_units > 0 && (!d_H || !d_C)) { set_error("aomhip_calc_proj_params_batch: invalid argument"); return AOMHIP_ERR_INVALID; }
   if (n_units == 0) return AOMHIP_OK;
-  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
-  if (src->bit_depth == 8)
-    hipLaunchKernelGGL(proj_params_kernel<uint8_t>, dim3(n_units), dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(src->base) + so, src->stride,
-                       static_cast<const uint8_t *>(dat->base) + po, dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_H, d_C);
-  else
-    hipLaunchKernelGGL(proj_params_kernel<uint16_t>, dim3(n_units), dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(src->base) + so, src->stride,
-                       static_cast<const uint16_t *>(dat->base) + po, dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_H, d_C);
+  with_pixel(src->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(proj_params_kernel<T>, dim3(n_units), dim3(256), 0, ctx->stream, pixels<T>(src, src_frame), src->stride, pixels<T>(dat, dat_frame),
+                       dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_H, d_C);
+  });
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -504,14 +420,11 @@ extern "C" int aomhip_pixel_proj_error_batch(aomhip_ctx *ctx, const aomhip_plane
   if (rc != AOMHIP_OK) return rc;
   if (n_xq < 0 || n_xq > 65535 || (n_units > 0 && n_xq > 0 && (!d_xq || !d_err))) { set_error("aomhip_pixel_proj_error_batch: invalid argument"); return AOMHIP_ERR_INVALID; }
   if (n_units == 0 || n_xq == 0) return AOMHIP_OK;
-  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
-  if (src->bit_depth == 8)
-    hipLaunchKernelGGL(proj_error_kernel<uint8_t>, dim3(n_units, n_xq), dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(src->base) + so, src->stride,
-                       static_cast<const uint8_t *>(dat->base) + po, dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_xq, n_xq, d_err);
-  else
-    hipLaunchKernelGGL(proj_error_kernel<uint16_t>, dim3(n_units, n_xq), dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(src->base) + so, src->stride,
-                       static_cast<const uint16_t *>(dat->base) + po, dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_xq, n_xq, d_err);
+  with_pixel(src->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(proj_error_kernel<T>, dim3(n_units, n_xq), dim3(256), 0, ctx->stream, pixels<T>(src, src_frame), src->stride, pixels<T>(dat, dat_frame),
+                       dat->stride, d_units, d_flt0, d_flt1, flt_stride, flt_pitch, d_radii, d_xq, n_xq, d_err);
+  });
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -525,29 +438,10 @@ extern "C" int aomhip_selfguided_restoration_batch(aomhip_ctx *ctx, const aomhip
     set_error("aomhip_selfguided_restoration_batch: invalid argument (border >= 3; flt_stride / flt_pitch hold the largest unit)");
     return AOMHIP_ERR_INVALID;
   }
-  for (int i = 0; h_units && i < n_units; ++i) {
-    const aomhip_rect &r = h_units[i];
-    if (r.h_start < 0 || r.v_start < 0 || r.h_end > dgd->width || r.v_end > dgd->height || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-        r.h_end - r.h_start > max_unit_width || r.v_end - r.v_start > max_unit_height) {
-      set_error("aomhip_selfguided_restoration_batch: unit %d is empty, outside the plane or larger than the stated maximum", i);
-      return AOMHIP_ERR_INVALID;
-    }
-  }
+  if (!check_unit_list("aomhip_selfguided_restoration_batch", h_units, n_units, dgd->width, dgd->height, max_unit_width, max_unit_height)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
   launch_selfguided(ctx, dgd, dgd_frame, d_units, n_units, d_sgr_params_idx, max_unit_width, max_unit_height, d_flt0, d_flt1, flt_stride, flt_pitch);
   AOMHIP_LAUNCH_CHECK();
-  return AOMHIP_OK;
-}
-
-static int check_lr_units(const aomhip_planes *dat, const aomhip_rect *h_units, int n_units, int max_w, int max_h, const char *who) {
-  for (int i = 0; h_units && i < n_units; ++i) {
-    const aomhip_rect &r = h_units[i];
-    if (r.h_start < 0 || r.v_start < 0 || r.h_end > dat->width || r.v_end > dat->height || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-        r.h_end - r.h_start > max_w || r.v_end - r.v_start > max_h) {
-      set_error("%s: unit %d is empty, outside the plane or larger than the stated maximum", who, i);
-      return AOMHIP_ERR_INVALID;
-    }
-  }
   return AOMHIP_OK;
 }
 
@@ -563,17 +457,14 @@ extern "C" int aomhip_apply_selfguided_restoration_batch(aomhip_ctx *ctx, const 
   int rc = aomhip_selfguided_restoration_batch(ctx, dat, dat_frame, d_units, h_units, n_units, d_sgr_params_idx, max_unit_width, max_unit_height, d_flt0, d_flt1,
                                                flt_stride, flt_pitch);
   if (rc != AOMHIP_OK || n_units == 0) return rc;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
-  const int64_t qo = (int64_t)dst_frame * dst->frame_stride + (int64_t)dst->border * dst->stride + dst->border;
   const int chunks = (max_unit_width * max_unit_height + 256 * 16 - 1) / (256 * 16);
   const dim3 grid((unsigned)n_units, (unsigned)(chunks < 1 ? 1 : chunks));
-  if (dat->bit_depth == 8)
-    hipLaunchKernelGGL(selfguided_apply_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(dat->base) + po, dat->stride,
-                       static_cast<uint8_t *>(dst->base) + qo, dst->stride, d_units, d_sgr_params_idx, d_xqd, 8, d_flt0, d_flt1, flt_stride, flt_pitch, dat->width, dat->height, max_unit_width, max_unit_height);
-  else
-    hipLaunchKernelGGL(selfguided_apply_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(dat->base) + po, dat->stride,
-                       static_cast<uint16_t *>(dst->base) + qo, dst->stride, d_units, d_sgr_params_idx, d_xqd, dat->bit_depth, d_flt0, d_flt1, flt_stride,
-                       flt_pitch, dat->width, dat->height, max_unit_width, max_unit_height);
+  with_pixel(dat->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(selfguided_apply_kernel<T>, grid, dim3(256), 0, ctx->stream, pixels<T>(dat, dat_frame), dat->stride, pixels<T>(dst, dst_frame), dst->stride,
+                       d_units, d_sgr_params_idx, d_xqd, dat->bit_depth, d_flt0, d_flt1, flt_stride, flt_pitch, dat->width, dat->height, max_unit_width,
+                       max_unit_height);
+  });
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -587,18 +478,15 @@ extern "C" int aomhip_wiener_convolve_add_src_batch(aomhip_ctx *ctx, const aomhi
     set_error("aomhip_wiener_convolve_add_src_batch: invalid argument (border >= 3)");
     return AOMHIP_ERR_INVALID;
   }
-  if (int rc = check_lr_units(dat, h_units, n_units, max_unit_width, max_unit_height, "aomhip_wiener_convolve_add_src_batch")) return rc;
+  if (!check_unit_list("aomhip_wiener_convolve_add_src_batch", h_units, n_units, dat->width, dat->height, max_unit_width, max_unit_height)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
   const int tiles_x = (max_unit_width + kWienerTile - 1) / kWienerTile, tiles_y = (max_unit_height + kWienerTile - 1) / kWienerTile;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
-  const int64_t qo = (int64_t)dst_frame * dst->frame_stride + (int64_t)dst->border * dst->stride + dst->border;
   const dim3 grid((unsigned)n_units, (unsigned)(tiles_x * tiles_y));
-  if (dat->bit_depth == 8)
-    hipLaunchKernelGGL(wiener_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint8_t *>(dat->base) + po, dat->stride,
-                       static_cast<uint8_t *>(dst->base) + qo, dst->stride, d_units, d_filters, 8, tiles_x, dat->width, dat->height, max_unit_width, max_unit_height);
-  else
-    hipLaunchKernelGGL(wiener_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, static_cast<const uint16_t *>(dat->base) + po, dat->stride,
-                       static_cast<uint16_t *>(dst->base) + qo, dst->stride, d_units, d_filters, dat->bit_depth, tiles_x, dat->width, dat->height, max_unit_width, max_unit_height);
+  with_pixel(dat->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(wiener_kernel<T>, grid, dim3(256), 0, ctx->stream, pixels<T>(dat, dat_frame), dat->stride, pixels<T>(dst, dst_frame), dst->stride, d_units,
+                       d_filters, dat->bit_depth, tiles_x, dat->width, dat->height, max_unit_width, max_unit_height);
+  });
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

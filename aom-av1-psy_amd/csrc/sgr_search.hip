@@ -19,16 +19,13 @@
 
 #include "restoration_device.h"
 #include "search_chain.h"
-#include "sgr_table.inc"
 
 namespace aomhip {
 
-constexpr int kSgrSearchMaxUnit = 384;                 // 1.5 RESTORATION_UNITSIZE_MAX: the largest unit av1_foreach_rest_unit_in_row hands out
 constexpr size_t kFltBudget = (size_t)512 << 20;       // flt0 + flt1 of one chunk of units: 42 units of 256 x 368 with all 16 sets, 672 workgroups
 constexpr int kBigUnitPixels = 128 * 128;              // above it a list entry gets 1024 lanes
 constexpr int kPrjBits = 7;                            // SGRPROJ_PRJ_BITS
 constexpr int kPrjMin0 = -96, kPrjMax0 = 31, kPrjMin1 = -32, kPrjMax1 = 95;   // SGRPROJ_PRJ_MIN0 .. MAX1 (av1/common/restoration.h)
-__device__ const int kSearchSgrParams[16][4] = AOMHIP_SGR_PARAMS;
 // pickrst.c:44-53
 __device__ const int8_t kEpGrp1Seed[4] = { 0, 3, 6, 9 };
 __device__ const int8_t kEpGrp23[2][14] = { { 10, 10, 11, 11, 12, 12, 13, 13, 13, 13, -1, -1, -1, -1 }, { 14, 14, 14, 14, 14, 14, 14, 15, 15, 15, 15, 15, 15, 15 } };
@@ -82,7 +79,6 @@ __global__ __launch_bounds__(256) void sgr_plan_kernel(const aomhip_rect *__rest
 __device__ __forceinline__ int64_t signed_rounded_divide(int64_t dividend, int64_t divisor) {
   return dividend < 0 ? (dividend - divisor / 2) / divisor : (dividend + divisor / 2) / divisor;
 }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 // one numerator of get_proj_subspace's 2 x 2 solve (:716-729): if scaling up the dividend would overflow, the divisor is scaled down instead
 __device__ __forceinline__ int solve_tap(int64_t div, int64_t det) {
@@ -98,12 +94,10 @@ template <typename T, int NT> struct UnitPixels {
   const int32_t *f0, *f1;
   int src_stride, dat_stride, flt_stride, w, n, r0, r1;
 
-  // get_pixel_proj_error (:373-399) of xqd: av1_decode_xq (restoration.c:631-643), then av1_[lowbd|highbd]_pixel_proj_error (:226-370)
+  // get_pixel_proj_error (:373-399) of xqd: av1_decode_xq, then av1_[lowbd|highbd]_pixel_proj_error (:226-370; the projection: restoration_device.h)
   __device__ __forceinline__ long long error(int xqd0, int xqd1, long long *scratch) const {
     int xq0, xq1;
-    if (r0 == 0) { xq0 = 0; xq1 = (1 << kPrjBits) - xqd1; }
-    else if (r1 == 0) { xq0 = xqd0; xq1 = 0; }
-    else { xq0 = xqd0; xq1 = (1 << kPrjBits) - xq0 - xqd1; }
+    sgr_decode_xq(r0, r1, xqd0, xqd1, xq0, xq1);
     const int di = NT / w, dj = NT - di * w;
     int i = (int)threadIdx.x / w, j = (int)threadIdx.x - i * w;
     long long err = 0;
@@ -111,10 +105,8 @@ template <typename T, int NT> struct UnitPixels {
     for (int t = threadIdx.x; t < n; t += NT) {
       const int d = (int)dat[(int64_t)i * dat_stride + j], sv = (int)src[(int64_t)i * src_stride + j];
       const int uu = d << 4;                               // SGRPROJ_RST_BITS
-      int v = 1 << 10;                                     // half of 1 << (SGRPROJ_RST_BITS + SGRPROJ_PRJ_BITS)
-      if (r0 > 0) v += xq0 * (f0[(int64_t)i * flt_stride + j] - uu);
-      if (r1 > 0) v += xq1 * (f1[(int64_t)i * flt_stride + j] - uu);
-      const int e = (v >> 11) + d - sv;
+      const int64_t fo = (int64_t)i * flt_stride + j;
+      const int e = sgr_proj_round(sgr_proj_terms(uu, r0, r1, xq0, xq1, f0 + fo, f1 + fo)) + d - sv;
       err += (long long)e * e;
       i += di; j += dj;
       if (j >= w) { j -= w; ++i; }
@@ -180,7 +172,7 @@ __global__ __launch_bounds__(NT) void sgr_eval_kernel(const T *__restrict__ src,
   pix.f0 = flt0 + (int64_t)e * flt_pitch; pix.f1 = flt1 + (int64_t)e * flt_pitch;
   pix.src_stride = src_stride; pix.dat_stride = dat_stride; pix.flt_stride = flt_stride;
   pix.w = w; pix.n = w * h;
-  const int r0 = pix.r0 = kSearchSgrParams[ep][0], r1 = pix.r1 = kSearchSgrParams[ep][1];
+  const int r0 = pix.r0 = kSgrParams[ep][0], r1 = pix.r1 = kSgrParams[ep][1];
 
   // av1_calc_proj_params[_high_bd] (:470-657): H, C over the radii in use, each divided by the unit's size with C's truncation
   long long h00 = 0, h01 = 0, h11 = 0, c0 = 0, c1 = 0;
@@ -238,17 +230,11 @@ __global__ __launch_bounds__(NT) void sgr_eval_kernel(const T *__restrict__ src,
 }
 
 template <typename T, int NT>
-static void launch_eval_t(hipStream_t st, int n_ent, const aomhip_planes *src, int64_t so, const aomhip_planes *dat, int64_t po, const aomhip_rect *ent_units,
-                          const int32_t *ent_ep, int count, const int32_t *flt0, const int32_t *flt1, int flt_stride, int64_t flt_pitch,
-                          aomhip_sgr_search_result *per_ep) {
-  hipLaunchKernelGGL((sgr_eval_kernel<T, NT>), dim3(n_ent), dim3(NT), 0, st, static_cast<const T *>(src->base) + so, src->stride,
-                     static_cast<const T *>(dat->base) + po, dat->stride, ent_units, ent_ep, count, flt0, flt1, flt_stride, flt_pitch, per_ep);
-}
-static void launch_eval(hipStream_t st, int bd, bool big, int n_ent, const aomhip_planes *src, int64_t so, const aomhip_planes *dat, int64_t po,
-                        const aomhip_rect *ent_units, const int32_t *ent_ep, int count, const int32_t *flt0, const int32_t *flt1, int flt_stride,
-                        int64_t flt_pitch, aomhip_sgr_search_result *per_ep) {
-  auto f = bd == 8 ? (big ? launch_eval_t<uint8_t, 1024> : launch_eval_t<uint8_t, 256>) : (big ? launch_eval_t<uint16_t, 1024> : launch_eval_t<uint16_t, 256>);
-  f(st, n_ent, src, so, dat, po, ent_units, ent_ep, count, flt0, flt1, flt_stride, flt_pitch, per_ep);
+static void launch_eval_t(hipStream_t st, int n_ent, const aomhip_planes *src, int src_frame, const aomhip_planes *dat, int dat_frame,
+                          const aomhip_rect *ent_units, const int32_t *ent_ep, int count, const int32_t *flt0, const int32_t *flt1, int flt_stride,
+                          int64_t flt_pitch, aomhip_sgr_search_result *per_ep) {
+  hipLaunchKernelGGL((sgr_eval_kernel<T, NT>), dim3(n_ent), dim3(NT), 0, st, pixels<T>(src, src_frame), src->stride, pixels<T>(dat, dat_frame), dat->stride,
+                     ent_units, ent_ep, count, flt0, flt1, flt_stride, flt_pitch, per_ep);
 }
 
 // the chunk of units whose flt0 / flt1 fit kFltBudget, and the layout of a call's work memory
@@ -274,7 +260,6 @@ size_t search_selfguided_bytes(int n_units, int max_w, int max_h, int pruning, b
 
 void search_selfguided_ws(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dat, int dat_frame, const aomhip_rect *d_units,
                           int n_units, int max_w, int max_h, int pruning, aomhip_sgr_search_result *d_best, aomhip_sgr_search_result *d_per_ep, char *ws) {
-  const int bd = dat->bit_depth;
   const SgrStages st = stages_of(pruning);
   const int flt_stride = max_w;
   const int64_t flt_pitch = (int64_t)flt_stride * max_h;
@@ -286,8 +271,6 @@ void search_selfguided_ws(aomhip_ctx *ctx, const aomhip_planes *src, int src_fra
   int32_t *flt0 = w.flt0, *flt1 = w.flt1, **ent_ep = w.ent_ep, *ent_idx = w.ent_idx;
   aomhip_rect *ent_units = w.ent_units;
   aomhip_sgr_search_result *per_ep = d_per_ep ? d_per_ep : w.per_ep;
-  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
-  const int64_t po = (int64_t)dat_frame * dat->frame_stride + (int64_t)dat->border * dat->stride + dat->border;
   for (int c0 = 0; c0 < n_units; c0 += chunk) {
     const int n = min(chunk, n_units - c0);
     for (int s = 0; s <= st.n; ++s) {   // (the last round only folds the last stage)
@@ -297,7 +280,11 @@ void search_selfguided_ws(aomhip_ctx *ctx, const aomhip_planes *src, int src_fra
                          per_ep + 16 * (int64_t)c0, d_best + c0);
       if (count == 0) break;
       launch_selfguided(ctx, dat, dat_frame, ent_units, n * count, ent_idx, max_w, max_h, flt0, flt1, flt_stride, flt_pitch);
-      launch_eval(ctx->stream, bd, big, n * count, src, so, dat, po, ent_units, ent_ep[s], count, flt0, flt1, flt_stride, flt_pitch, per_ep + 16 * (int64_t)c0);
+      with_pixel(dat->bit_depth, [&](auto px) {
+        using T = decltype(px);
+        auto eval = big ? launch_eval_t<T, 1024> : launch_eval_t<T, 256>;
+        eval(ctx->stream, n * count, src, src_frame, dat, dat_frame, ent_units, ent_ep[s], count, flt0, flt1, flt_stride, flt_pitch, per_ep + 16 * (int64_t)c0);
+      });
     }
   }
 }
@@ -315,25 +302,10 @@ extern "C" int aomhip_search_selfguided_restoration_batch(aomhip_ctx *ctx, const
     set_error("%s: invalid argument (border of the degraded plane >= 3)", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int bd = dat->bit_depth;
-  if ((bd != 8 && bd != 10 && bd != 12) || src->bit_depth != bd || src->width != dat->width || src->height != dat->height) {
-    set_error("%s: the two rings differ in bit depth (%d / %d; 8, 10 or 12) or geometry", who, src->bit_depth, bd);
-    return AOMHIP_ERR_INVALID;
-  }
-  int max_w = kSgrSearchMaxUnit, max_h = kSgrSearchMaxUnit;
-  if (h_units) {
-    max_w = 1; max_h = 1;
-    for (int i = 0; i < n_units; ++i) {
-      const aomhip_rect &r = h_units[i];
-      if (r.h_start < 0 || r.v_start < 0 || r.h_end > dat->width || r.v_end > dat->height || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-          r.h_end - r.h_start > kSgrSearchMaxUnit || r.v_end - r.v_start > kSgrSearchMaxUnit) {
-        set_error("%s: unit %d is empty, outside the %d x %d plane or larger than %d", who, i, dat->width, dat->height, kSgrSearchMaxUnit);
-        return AOMHIP_ERR_INVALID;
-      }
-      max_w = max(max_w, r.h_end - r.h_start); max_h = max(max_h, r.v_end - r.v_start);
-    }
-  }
+  UnitListExtent ext;
+  if (!check_rings(who, { dat, src }) || !check_unit_list(who, h_units, n_units, dat->width, dat->height, kLrMaxUnit, kLrMaxUnit, &ext)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
+  const int max_w = ext.w, max_h = ext.h;
 
   const int pruning = enable_sgr_ep_pruning != 0;
   char *ws;

@@ -36,7 +36,6 @@ constexpr int kWienerIters = 5;                        // NUM_WIENER_ITERS
 __device__ __forceinline__ int tap_mid(int p) { return p == 0 ? 3 : p == 1 ? -7 : p == 2 ? 15 : 128 - 2 * (3 - 7 + 15); }
 __device__ __forceinline__ int tap_min(int p) { return p == 0 ? -5 : p == 1 ? -23 : -17; }
 __device__ __forceinline__ int tap_max(int p) { return p == 0 ? 10 : p == 1 ? 8 : 46; }
-__device__ __forceinline__ int clipi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 __global__ __launch_bounds__(256) void wiener_prep_kernel(const aomhip_rect *__restrict__ units, int n_units, int plane_w, int plane_h,
                                                           aomhip_rect *__restrict__ clipped) {
@@ -49,7 +48,6 @@ __device__ __forceinline__ int64_t wave_sum(int64_t v) {
   for (int m = 1; m < 64; m <<= 1) v += __shfl_xor((long long)v, m, 64);
   return v;
 }
-__device__ __forceinline__ int64_t abs64(int64_t v) { return v < 0 ? -v : v; }   // llabs
 
 // linsolve_wiener (:1089-1129) for n = N unknowns, A with rows STRIDE apart; fully unrolled, every index static.  A and b are changed as there.
 template <int N, int STRIDE> __device__ __forceinline__ int linsolve_wiener(int64_t (&A)[STRIDE * STRIDE], int64_t (&b)[STRIDE], int64_t (&x)[N]) {
@@ -102,12 +100,12 @@ template <int WIN> __device__ __forceinline__ void finalize_sym_filter(const int
     fi[i] = (int)(int16_t)(dividend < 0 ? (dividend - divisor / 2) / divisor : (dividend + divisor / 2) / divisor);
   }
   if (WIN == 7) {
-    fi[0] = clipi(fi[0], tap_min(0), tap_max(0));
-    fi[1] = clipi(fi[1], tap_min(1), tap_max(1));
-    fi[2] = clipi(fi[2], tap_min(2), tap_max(2));
+    fi[0] = clampi(fi[0], tap_min(0), tap_max(0));
+    fi[1] = clampi(fi[1], tap_min(1), tap_max(1));
+    fi[2] = clampi(fi[2], tap_min(2), tap_max(2));
   } else {
-    fi[2] = clipi(fi[1], tap_min(2), tap_max(2));
-    fi[1] = clipi(fi[0], tap_min(1), tap_max(1));
+    fi[2] = clampi(fi[1], tap_min(2), tap_max(2));
+    fi[1] = clampi(fi[0], tap_min(1), tap_max(1));
     fi[0] = 0;
   }
 }
@@ -281,9 +279,9 @@ __global__ __launch_bounds__(NT) void wiener_walk_kernel(const T *__restrict__ s
     return;
   }
 
-  const int SH = 64 >> ss_y, off = 8 >> ss_y, pps = SH / kLrPH;
-  const int k0 = (u.v_start + off) / SH, n_stripes = (u.v_end - 1 + off) / SH - k0 + 1;
-  const int tiles_x = (w + kLrPW - 1) / kLrPW, n_pieces = n_stripes * pps * tiles_x;
+  const int SH = 64 >> ss_y, off = 8 >> ss_y;
+  const int n_stripes = (u.v_end - 1 + off) / SH - (u.v_start + off) / SH + 1;
+  const int tiles_x = (w + kLrPW - 1) / kLrPW, n_pieces = n_stripes * (SH / kLrPH) * tiles_x;
   int taps[6] = { r.hfilter[0], r.hfilter[1], r.hfilter[2], r.vfilter[0], r.vfilter[1], r.vfilter[2] };
   int n_trials = 0;
 
@@ -297,14 +295,9 @@ __global__ __launch_bounds__(NT) void wiener_walk_kernel(const T *__restrict__ s
     fv[3] = -2 * (taps[3] + taps[4] + taps[5]);
     long long err = 0;
     for (int t0 = 0; t0 < n_pieces; t0 += G) {
-      const int t = t0 + g;
-      const int p = t / tiles_x, tx = t - p * tiles_x;
-      const int ox = u.h_start + tx * kLrPW;
-      const int k = k0 + p / pps;
-      const int y0 = max(max(0, k * SH - off), u.v_start), y1 = min(min((k + 1) * SH - off, plane_h), u.v_end);
-      const int py0 = y0 + (p % pps) * kLrPH, py1 = min(py0 + kLrPH, y1);
-      const bool active = t < n_pieces && py0 < py1;   // (the first stripe of a plane is 8 >> ss_y rows short: its second piece can be empty)
-      const int pw = min(kLrPW, u.h_end - ox), ph = py1 - py0;
+      const LrPiece pc = lr_piece_of(u, t0 + g, tiles_x, ss_y, plane_h);
+      const bool active = t0 + g < n_pieces && !pc.empty;   // (the first stripe of a plane is 8 >> ss_y rows short: its second piece can be empty)
+      const int ox = pc.ox, py0 = pc.py0, pw = pc.pw, ph = pc.ph;
       // the source pixels of this lane first, from addresses clamped into the piece: their latency hides behind the two passes (behind the bounds
       // test below the loads could not move up, and a lane would wait for each of them in turn)
       int sv[kLrPerLane];
@@ -312,7 +305,7 @@ __global__ __launch_bounds__(NT) void wiener_walk_kernel(const T *__restrict__ s
       for (int q = 0; q < kLrPerLane; ++q)
         sv[q] = active ? (int)src[(int64_t)(py0 + min(lr_row(tid, q), ph - 1)) * src_stride + min(ox + lx, u.h_end - 1)] : 0;
       __syncthreads();                                 // the piece before has been read
-      if (active) lr_stage_footprint(s_d[g], tid, deb, deb_stride, cdef, cdef_stride, ox, py0, y0, y1, plane_w, plane_h);
+      if (active) lr_stage_footprint(s_d[g], tid, deb, deb_stride, cdef, cdef_stride, ox, py0, pc.y0, pc.y1, plane_w, plane_h);
       __syncthreads();
       if (active) lr_wiener_hpass(s_d[g], s_tmp[g], tid, ph, fh, bd);
       __syncthreads();
@@ -379,11 +372,10 @@ __global__ __launch_bounds__(NT) void wiener_walk_kernel(const T *__restrict__ s
 }
 
 template <typename T, int NT>
-static void launch_walk_t(hipStream_t st, int n, const aomhip_planes *src, int64_t so, const aomhip_planes *deb, int64_t eo, const aomhip_planes *cdef,
-                          int64_t co, const aomhip_rect *units, int ss_y, int win, aomhip_wiener_search_result *res, aomhip_wiener_trial *trace) {
-  hipLaunchKernelGGL((wiener_walk_kernel<T, NT>), dim3(n), dim3(NT), 0, st, static_cast<const T *>(src->base) + so, src->stride,
-                     static_cast<const T *>(deb->base) + eo, deb->stride, static_cast<const T *>(cdef->base) + co, cdef->stride, units, cdef->bit_depth,
-                     cdef->width, cdef->height, ss_y, win, res, trace);
+static void launch_walk_t(hipStream_t st, int n, const aomhip_planes *src, int src_frame, const aomhip_planes *deb, int deb_frame, const aomhip_planes *cdef,
+                          int cdef_frame, const aomhip_rect *units, int ss_y, int win, aomhip_wiener_search_result *res, aomhip_wiener_trial *trace) {
+  hipLaunchKernelGGL((wiener_walk_kernel<T, NT>), dim3(n), dim3(NT), 0, st, pixels<T>(src, src_frame), src->stride, pixels<T>(deb, deb_frame), deb->stride,
+                     pixels<T>(cdef, cdef_frame), cdef->stride, units, cdef->bit_depth, cdef->width, cdef->height, ss_y, win, res, trace);
 }
 
 // the chunk of units whose M / H fit kStatsBudget, and the layout of a call's work memory
@@ -402,29 +394,29 @@ size_t search_wiener_bytes(int n_units, int wiener_win) {
   return carve_bytes([&](WorkCarver &c) { w.layout(c, wiener_chunk(n_units, wiener_win), wiener_win * wiener_win); });
 }
 
-void search_wiener_ws(aomhip_ctx *ctx, const aomhip_planes *src, int64_t so, const aomhip_planes *deblocked, int64_t eo, const aomhip_planes *cdef,
-                      int64_t co, int ss_y, int wiener_win, const aomhip_rect *d_units, int n_units, bool big, int use_downsampled_wiener_stats,
+void search_wiener_ws(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *deblocked, int deblocked_frame, const aomhip_planes *cdef,
+                      int cdef_frame, int ss_y, int wiener_win, const aomhip_rect *d_units, int n_units, bool big, int use_downsampled_wiener_stats,
                       aomhip_wiener_search_result *d_result, aomhip_wiener_trial *d_trace, char *ws) {
-  const int bd = cdef->bit_depth, plane_w = cdef->width, plane_h = cdef->height;
   const int chunk = wiener_chunk(n_units, wiener_win);
   WienerWork w;
   WorkCarver carver{ ws };
   w.layout(carver, chunk, wiener_win * wiener_win);
   int64_t *M = w.M, *H = w.H;
   aomhip_rect *clipped = w.clipped;
-  const size_t esz = bd == 8 ? 1 : 2;
-  auto walk = bd == 8 ? (big ? launch_walk_t<uint8_t, 1024> : launch_walk_t<uint8_t, 256>) : (big ? launch_walk_t<uint16_t, 1024> : launch_walk_t<uint16_t, 256>);
   for (int c0 = 0; c0 < n_units; c0 += chunk) {
     const int n = min(chunk, n_units - c0);
-    hipLaunchKernelGGL(wiener_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, plane_w, plane_h, clipped);
-    launch_wiener_stats(ctx->stream, bd, wiener_win, true, n, static_cast<const char *>(cdef->base) + co * esz, cdef->stride,
-                        static_cast<const char *>(src->base) + so * esz, src->stride, clipped, use_downsampled_wiener_stats != 0, M, H);
+    hipLaunchKernelGGL(wiener_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_units + c0, n, cdef->width, cdef->height, clipped);
+    launch_wiener_stats(ctx->stream, wiener_win, true, n, cdef, cdef_frame, src, src_frame, clipped, use_downsampled_wiener_stats != 0, M, H);
     if (wiener_win == 7)
       hipLaunchKernelGGL(wiener_solve_kernel<7>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
     else
       hipLaunchKernelGGL(wiener_solve_kernel<5>, dim3(n), dim3(64), 0, ctx->stream, clipped, M, H, d_result + c0);
-    walk(ctx->stream, n, src, so, deblocked, eo, cdef, co, clipped, ss_y, wiener_win, d_result + c0,
-         d_trace ? d_trace + (int64_t)c0 * AOMHIP_WIENER_MAX_TRIALS : nullptr);
+    with_pixel(cdef->bit_depth, [&](auto px) {
+      using T = decltype(px);
+      auto walk = big ? launch_walk_t<T, 1024> : launch_walk_t<T, 256>;
+      walk(ctx->stream, n, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, clipped, ss_y, wiener_win, d_result + c0,
+           d_trace ? d_trace + (int64_t)c0 * AOMHIP_WIENER_MAX_TRIALS : nullptr);
+    });
   }
 }
 
@@ -443,44 +435,19 @@ extern "C" int aomhip_search_wiener_batch(aomhip_ctx *ctx, const aomhip_planes *
     set_error("%s: invalid argument (window 7 or 5; ss_y 0 or 1; border of the CDEF plane >= 3)", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int bd = cdef->bit_depth;
-  if ((bd != 8 && bd != 10 && bd != 12) || src->bit_depth != bd || deblocked->bit_depth != bd || src->width != cdef->width || src->height != cdef->height ||
-      deblocked->width != cdef->width || deblocked->height != cdef->height) {
-    set_error("%s: the three rings differ in bit depth (%d / %d / %d; 8, 10 or 12) or geometry", who, src->bit_depth, deblocked->bit_depth, bd);
-    return AOMHIP_ERR_INVALID;
-  }
-  if (use_downsampled_wiener_stats && bd != 8) {
+  if (!check_rings(who, { cdef, src, deblocked })) return AOMHIP_ERR_INVALID;
+  if (use_downsampled_wiener_stats && cdef->bit_depth != 8) {
     set_error("%s: the down-sampled statistics exist for 8 bits only", who);
     return AOMHIP_ERR_INVALID;
   }
-  const int plane_w = cdef->width, plane_h = cdef->height;
-  const int SH = 64 >> ss_y, off = 8 >> ss_y;
-  bool big = true;
-  if (h_units) {
-    big = false;
-    for (int i = 0; i < n_units; ++i) {
-      const aomhip_rect &r = h_units[i];
-      if (r.h_start < 0 || r.v_start < 0 || r.h_end > plane_w || r.v_end > plane_h || r.h_end <= r.h_start || r.v_end <= r.v_start ||
-          r.h_end - r.h_start > kLrMaxUnit || r.v_end - r.v_start > kLrMaxUnit) {
-        set_error("%s: unit %d is empty, outside the %d x %d plane or larger than %d", who, i, plane_w, plane_h, kLrMaxUnit);
-        return AOMHIP_ERR_INVALID;
-      }
-      if ((r.v_end != plane_h && (r.v_end + off) % SH != 0) || (r.v_start != 0 && (r.v_start + off) % SH != 0)) {
-        set_error("%s: unit %d covers rows %d .. %d: a unit starts at row 0 or a stripe boundary k * %d - %d and ends at one or at the plane's bottom", who, i,
-                  r.v_start, r.v_end, SH, off);
-        return AOMHIP_ERR_INVALID;
-      }
-      big = big || (r.h_end - r.h_start) * (r.v_end - r.v_start) > kWalkBigUnitPixels;
-    }
-  }
+  UnitListExtent ext;
+  if (!check_unit_list(who, h_units, n_units, cdef->width, cdef->height, kLrMaxUnit, kLrMaxUnit, &ext, ss_y)) return AOMHIP_ERR_INVALID;
   if (n_units == 0) return AOMHIP_OK;
 
   char *ws;
   if (!carve_work(ctx, [&](WorkCarver &c) { c(ws, search_wiener_bytes(n_units, wiener_win)); })) return AOMHIP_ERR_HIP;
-  const int64_t so = (int64_t)src_frame * src->frame_stride + (int64_t)src->border * src->stride + src->border;
-  const int64_t eo = (int64_t)deblocked_frame * deblocked->frame_stride + (int64_t)deblocked->border * deblocked->stride + deblocked->border;
-  const int64_t co = (int64_t)cdef_frame * cdef->frame_stride + (int64_t)cdef->border * cdef->stride + cdef->border;
-  search_wiener_ws(ctx, src, so, deblocked, eo, cdef, co, ss_y, wiener_win, d_units, n_units, big, use_downsampled_wiener_stats, d_result, d_trace, ws);
+  search_wiener_ws(ctx, src, src_frame, deblocked, deblocked_frame, cdef, cdef_frame, ss_y, wiener_win, d_units, n_units, ext.pixels > kWalkBigUnitPixels,
+                   use_downsampled_wiener_stats, d_result, d_trace, ws);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
