@@ -141,6 +141,10 @@ inline bool valid_block(int w, int h) {
   if (r == 4 && (w == 128 || h == 128)) return false;  // no 128x32 / 32x128
   return true;
 }
+// ... as a dispatch list: X(W, H) once per size
+#define AOMHIP_FOR_BLOCK_SIZES(X)                                                                                \
+  X(4, 4) X(4, 8) X(8, 4) X(8, 8) X(8, 16) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32) X(32, 64) X(64, 32) \
+  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
 
 }  // namespace aomhip
 #endif  // AOMHIP_CSRC_COMMON_H_

@@ -87,15 +87,13 @@ __global__ __launch_bounds__(SPEC * 64) void fp_row_kernel(PlaneView<T> src, Pla
         if (fr.var != INT_MAX) {
           // av1_get_mvpred_sse (mcomp.c:3661-3677): the sse of the mse function at the full-pel MV + mv_err_cost, + NEW_MV_MODE_PENALTY (:292-296)
           const T *rp = rbase + (int64_t)m1r * last.stride + m1c;
-          unsigned long long sse = 0;
+          int64_t sse = 0;
           for (int t = lane; t < W * H; t += 64) {
             const int y = t / W, x = t - y * W;
             const int d = (int)sp[(int64_t)y * src.stride + x] - (int)rp[(int64_t)y * last.stride + x];
             sse += (unsigned)__mul24(d, d);
           }
-#pragma unroll
-          for (int m = 1; m < 64; m <<= 1) sse += __shfl_xor(sse, m, 64);
-          const uint32_t qq = q.bit_depth == 10 ? (uint32_t)((sse + 8) >> 4) : q.bit_depth == 12 ? (uint32_t)((sse + 128) >> 8) : (uint32_t)sse;
+          const uint32_t qq = depth_sse((uint64_t)wave_sum64(sse), q.bit_depth);
           const int mrow = m1r * 8, mcol = m1c * 8;
           const int cost = C.err_cost(mrow, mcol, brow, bcol);
           e1 = (int32_t)(qq + (uint32_t)cost + 32u);

@@ -62,8 +62,7 @@ struct FpfCost {
   int type, error_per_bit; const int32_t *mvjcost, *mvcost0, *mvcost1;
   // mv_err_cost_ (mcomp.c:271-308) of the MV (mrow, mcol) around ref_mv, all in 1/8 pel
   __device__ __forceinline__ int err_cost(int mrow, int mcol, int ref_row, int ref_col) const {
-    if (type == kCostEntropy) return mv_err_cost_bits(mvjcost, mvcost0, mvcost1, mrow - ref_row, mcol - ref_col, error_per_bit);
-    return CostCtx{ type, ref_row, ref_col }.var_cost(mrow, mcol);
+    return MvCost<>(type, ref_row, ref_col, 0, error_per_bit, mvjcost, mvcost0, mvcost1).var(mrow, mcol);
   }
 };
 struct FpfOut { int16_t *best_mv, *full_mv; int32_t *motion_error, *gf_motion_error, *raw_motion_error; };

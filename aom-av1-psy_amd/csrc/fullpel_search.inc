@@ -36,10 +36,7 @@ __device__ __forceinline__ uint32_t group8_sad_mem(const T *sp, int sstride, con
       }
     }
   }
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-  return acc;
+  return row8_sum(acc);
 }
 
 // Blocks whose source rows do not fit the lanes' registers (G8::KEEP false: 32x32 on 16-bit planes and larger) read the source AND the
@@ -86,10 +83,7 @@ __device__ __forceinline__ uint32_t group8_sad_srclds(const uint32_t *src_lds, c
     }
     acc += acc1;
   }
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-  return acc;
+  return row8_sum(acc);
 }
 
 constexpr int kFpsThreads = 256;  // 4 blocks (wavefronts) per workgroup (the form without a window)
@@ -143,13 +137,15 @@ __device__ __forceinline__ void fps_block(const T *sp, int sstride, const T *rba
   const int g = lane >> 3, l = lane & 7;
   const int row_min = bs.row_min, row_max = bs.row_max, col_min = bs.col_min, col_max = bs.col_max, ref_row = bs.ref_row, ref_col = bs.ref_col;
   const int raw_start_row = bs.start_row, raw_start_col = bs.start_col;
-  const int frr = __builtin_amdgcn_readfirstlane((ref_row + 3 + (ref_row >= 0)) >> 3);  // get_fullmv_from_mv
-  const int frc = __builtin_amdgcn_readfirstlane((ref_col + 3 + (ref_col >= 0)) >> 3);
+  const int frr = __builtin_amdgcn_readfirstlane(rawpel(ref_row));  // get_fullmv_from_mv
+  const int frc = __builtin_amdgcn_readfirstlane(rawpel(ref_col));
   const int start_row = __builtin_amdgcn_readfirstlane(min(max(raw_start_row, row_min), row_max));  // clamp_fullmv
   const int start_col = __builtin_amdgcn_readfirstlane(min(max(raw_start_col, col_min), col_max));
   bool skip = !NOSKIP && q.skip_sad != 0;   // (NOSKIP: ms_params->sdf is the full SAD -- the row-skipping form and its re-check are compiled out)
   // the L1 cost types: mvsad_err_cost_ = (lambda * 8 d) >> 3 = lambda * d, mv_err_cost_ = (lambda' * d) >> 3
   const int lambda = q.cost_type == kCostL1Low ? 32 : q.cost_type == kCostL1Mid ? 15 : q.cost_type == kCostL1Hd ? 8 : 0;
+  // (L1_MIDRES's variance-stage lambda IS 0, mcomp.c:300, like NONE's: it takes the last arm -- written as its own `kCostL1Mid ? 0` arm the chain is not
+  // folded and full_pixel_search_kernel<uint16_t, 16, 4, 4> and <uint16_t, 8, 8, 4> go from 0 to 36 bytes of scratch; MvCost::var spells it out)
   const int lambda_var = q.cost_type == kCostL1Low ? 2 : q.cost_type == kCostL1Hd ? 1 : 0;
 
   typename G::L srcu[NU];
@@ -172,17 +168,15 @@ __device__ __forceinline__ void fps_block(const T *sp, int sstride, const T *rba
   auto check_bounds = [&](int r, int c, int range) {
     return (r - range) >= row_min && (r + range) <= row_max && (c - range) >= col_min && (c + range) <= col_max;
   };
-  auto mv_bits = [&](int dr, int dc) -> int {  // mv_cost (:250-254): joint + the two component tables, centre-addressed
-    return q.mvjcost[(dc != 0) | ((dr != 0) << 1)] + q.mvcost0[dr] + q.mvcost1[dc];
-  };
+  auto bits = [&](int dr, int dc) -> int { return mv_bits(q.mvjcost, q.mvcost0, q.mvcost1, dr, dc); };   // mv_cost (:250-254)
   auto sad_cost = [&](int row, int col) -> int {  // mvsad_err_cost_ (:310-339)
     const int dr = (row - frr) * 8, dc = (col - frc) * 8;
-    if (q.cost_type == kCostEntropy) return (int)(((unsigned)mv_bits(dr, dc) * (unsigned)q.sad_per_bit + 256u) >> 9);
+    if (q.cost_type == kCostEntropy) return (int)(((unsigned)bits(dr, dc) * (unsigned)q.sad_per_bit + 256u) >> 9);
     return lambda * (iabsm(row - frr) + iabsm(col - frc));
   };
   auto var_cost = [&](int mrow, int mcol) -> int {  // mv_err_cost_ (:271-308)
     const int dr = mrow - ref_row, dc = mcol - ref_col;
-    if (q.cost_type == kCostEntropy) return (int)(((int64_t)mv_bits(dr, dc) * q.error_per_bit + (1 << 13)) >> 14);
+    if (q.cost_type == kCostEntropy) return (int)(((int64_t)bits(dr, dc) * q.error_per_bit + (1 << 13)) >> 14);
     return (lambda_var * (iabsm(dr) + iabsm(dc))) >> 3;
   };
   // ms_params->sdf at (row0 + orow, col0 + ocol) evaluated by this lane's group: (row0, col0) uniform, (orow, ocol) the group's own
@@ -254,10 +248,7 @@ __device__ __forceinline__ void fps_block(const T *sp, int sstride, const T *rba
           }
         }
       }
-      v = a0 + a1;
-      v += __builtin_amdgcn_update_dpp(0u, v, 0xB1, 0xf, 0xf, false);
-      v += __builtin_amdgcn_update_dpp(0u, v, 0x4E, 0xf, 0xf, false);
-      v += __builtin_amdgcn_update_dpp(0u, v, 0x141, 0xf, 0xf, false);
+      v = row8_sum(a0 + a1);
     } else {
       bool from_lds = false;
       if constexpr (SrcLds<T, W, H>::USE) from_lds = src_lds != nullptr;
@@ -288,10 +279,7 @@ __device__ __forceinline__ void fps_block(const T *sp, int sstride, const T *rba
               a += 8 * (G::UB / 4);
             }
           }
-          v = a0 + a1;
-          v += __builtin_amdgcn_update_dpp(0u, v, 0xB1, 0xf, 0xf, false);
-          v += __builtin_amdgcn_update_dpp(0u, v, 0x4E, 0xf, 0xf, false);
-          v += __builtin_amdgcn_update_dpp(0u, v, 0x141, 0xf, 0xf, false);
+          v = row8_sum(a0 + a1);
           done = true;
         }
       }

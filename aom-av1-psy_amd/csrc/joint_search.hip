@@ -92,7 +92,7 @@ __global__ void joint_finish_kernel(int n, const int16_t *cur_mv, const int16_t 
   if (i >= n) return;
   int rate = 0;
   for (int r = 0; r < 2; ++r)   // av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266)
-    rate += mv_bit_cost(mvjcost, mvcost0, mvcost1, cur_mv[4 * i + 2 * r] - ref_mv[4 * i + 2 * r], cur_mv[4 * i + 2 * r + 1] - ref_mv[4 * i + 2 * r + 1]);
+    rate += mv_rate(mvjcost, mvcost0, mvcost1, cur_mv[4 * i + 2 * r] - ref_mv[4 * i + 2 * r], cur_mv[4 * i + 2 * r + 1] - ref_mv[4 * i + 2 * r + 1]);
   rate_mv[i] = rate;
   best_err[i] = last_besterr[2 * i] < last_besterr[2 * i + 1] ? last_besterr[2 * i] : last_besterr[2 * i + 1];
 }
@@ -221,7 +221,7 @@ __global__ void csingle_finish_kernel(int n, int force_integer_mv, const int16_t
   int bestsme = full_var[i], row = full_mv[2 * i] * 8, col = full_mv[2 * i + 1] * 8;   // convert_fullmv_to_mv (:773-775)
   if (bestsme < INT_MAX && !force_integer_mv) { bestsme = (int)sub_err[i]; row = sub_mv[2 * i]; col = sub_mv[2 * i + 1]; }
   if (bestsme < INT_MAX) { this_mv[2 * i] = (int16_t)row; this_mv[2 * i + 1] = (int16_t)col; }   // (:798)
-  rate_mv[i] = mv_bit_cost(mvjcost, mvcost0, mvcost1, this_mv[2 * i] - ref_mv[2 * i], this_mv[2 * i + 1] - ref_mv[2 * i + 1]);   // av1_mv_bit_cost(.., MV_COST_WEIGHT)
+  rate_mv[i] = mv_rate(mvjcost, mvcost0, mvcost1, this_mv[2 * i] - ref_mv[2 * i], this_mv[2 * i + 1] - ref_mv[2 * i + 1]);   // av1_mv_bit_cost(.., MV_COST_WEIGHT)
   bestsme_out[i] = bestsme;
 }
 }  // namespace

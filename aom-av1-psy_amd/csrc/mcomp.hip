@@ -80,11 +80,10 @@ __global__ __launch_bounds__(WAVES * 64, CELL ? 8 : 5) void fullpel_diamond_kern
   [[maybe_unused]] unsigned long long t_lds = 0, t_glob = 0, t_var = 0, n_lds = 0, n_glob = 0, n_var = 0;
   CELL_ADD(0, 1);
   CELL_ADD(1, CELL_T() - t_begin);
-  const CostCtx cc{ cost_type, b.ref_row, b.ref_col };
+  MvCost<false> mc(cost_type, b.ref_row, b.ref_col);   // (check_common: an L1 type or none)
+  mc.frr = __builtin_amdgcn_readfirstlane(mc.frr); mc.frc = __builtin_amdgcn_readfirstlane(mc.frc);   // (readfirstlane: as for the start MV)
   const int shift = bit_depth == 10 ? 2 : bit_depth == 12 ? 4 : 0;  // vtable wrappers for highbd SAD
-  const int lambda = cost_type == kCostL1Low ? 32 : cost_type == kCostL1Mid ? 15 : cost_type == kCostL1Hd ? 8 : 0;  // mvsad_err_cost_: (lambda * 8 d) >> 3
-  const int frr = __builtin_amdgcn_readfirstlane((b.ref_row + 3 + (b.ref_row >= 0)) >> 3);  // GET_MV_RAWPEL (readfirstlane: as for the start MV)
-  const int frc = __builtin_amdgcn_readfirstlane((b.ref_col + 3 + (b.ref_col >= 0)) >> 3);
+  const int lambda = mc.lambda_sad, frr = mc.frr, frc = mc.frc;   // (the rounds' own form of mvsad_err_cost_ below: v_sad_u32 against a bias)
   const int g = lane >> 3, l = lane & 7;
   const int dr = (g == 0 || g == 4 || g == 6) ? -1 : (g == 1 || g == 5 || g == 7) ? 1 : 0;   // site order of
   const int dc = (g == 2 || g == 4 || g == 7) ? -1 : (g == 3 || g == 5 || g == 6) ? 1 : 0;   // mcomp.c:366-370
@@ -160,11 +159,7 @@ __global__ __launch_bounds__(WAVES * 64, CELL ? 8 : 5) void fullpel_diamond_kern
           }
         }
       }
-      uint32_t acc = a0 + a1;
-      acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-      acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-      acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-      return acc;
+      return row8_sum(a0 + a1);
     } else {
       return group8_sad<T, W, H>(sp, src.stride, rbase + (int64_t)(row + dr * r) * ref.stride + (col + dc * r), ref.stride, l, active, srcu);
     }
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(WAVES * 64, CELL ? 8 : 5) void fullpel_diamond_kern
   uint32_t start_sad;
   {
     const uint32_t s0 = round_sad(start_row, start_col, 0, g == 0, win_covers(start_row, start_col, 0)) >> shift;
-    start_sad = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)__builtin_amdgcn_readlane((int)s0, 0) + (uint32_t)(lambda * (iabsm(start_row - frr) + iabsm(start_col - frc)))));
+    start_sad = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)__builtin_amdgcn_readlane((int)s0, 0) + (uint32_t)mc.sad(start_row, start_col)));
   }
 
   // How far the centre is from the nearest MV limit / from the nearest edge of the window (scalars): a round of radius r lies inside the
@@ -278,7 +273,7 @@ __global__ __launch_bounds__(WAVES * 64, CELL ? 8 : 5) void fullpel_diamond_kern
 #ifdef AOMHIP_CELL_PROF
     t_var += CELL_T() - t_v0; ++n_var;
 #endif
-    return (int)v + cc.var_cost(row * 8, col * 8);
+    return (int)v + mc.var(row * 8, col * 8);
   };
 
   // full_pixel_diamond (mcomp.c:1421-1470): the first search at step_param, then restarts at step_param + n that are
@@ -408,7 +403,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_search_kernel(
   const aomhip_search_block b = blocks[bi];
   const T *sp = src.origin + (int64_t)frame * src.frame_stride + (int64_t)b.by * src.stride + b.bx;
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)b.by * ref.stride + b.bx;
-  const CostCtx cc{ cost_type, b.ref_row, b.ref_col };
+  const MvCost<false> mc(cost_type, b.ref_row, b.ref_col);
   const int shift = bit_depth == 10 ? 2 : bit_depth == 12 ? 4 : 0;
 
   // source block -> LDS, packed rows
@@ -476,7 +471,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_search_kernel(
         else
           s0 = mesh_sad<T, W, H, false>(lds_src, reinterpret_cast<const char *>(rbase + (int64_t)srow * ref.stride + scol),
                                         (int64_t)ref.stride * ES);
-        const uint32_t t0 = (s0 >> shift) + (uint32_t)cc.sad_cost(srow, scol);
+        const uint32_t t0 = (s0 >> shift) + (uint32_t)mc.sad(srow, scol);
         key = (unsigned long long)t0 << 32;
       }
       for (int idx = tid; idx < n_cand; idx += kMeshThreads) {
@@ -489,7 +484,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_search_kernel(
           sad = mesh_sad<T, W, H, false>(lds_src,
                                          reinterpret_cast<const char *>(rbase + (int64_t)(srow + r) * ref.stride + scol + c),
                                          (int64_t)ref.stride * ES);
-        const uint32_t tot = (sad >> shift) + (uint32_t)cc.sad_cost(srow + r, scol + c);
+        const uint32_t tot = (sad >> shift) + (uint32_t)mc.sad(srow + r, scol + c);
         const unsigned long long k = ((unsigned long long)tot << 32) | (uint32_t)(idx + 1);
         key = k < key ? k : key;
       }
@@ -522,7 +517,7 @@ __global__ __launch_bounds__(kMeshThreads) void mesh_search_kernel(
       uint32_t sse;
       const uint32_t v = wave_variance<T, W, H, false>(rbase + (int64_t)br * ref.stride + bc, ref.stride, 0, 0, sp, src.stride,
                                                        /*a_minus_b=*/false, bit_depth, lane, &sse);
-      bestsme = (int)v + cc.var_cost(br * 8, bc * 8);
+      bestsme = (int)v + mc.var(br * 8, bc * 8);
     }
   }
   if (tid == 0) {

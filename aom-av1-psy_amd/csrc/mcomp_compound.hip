@@ -22,78 +22,14 @@ namespace {
 struct CompoundArgs {
   int bw, bh, bit_depth, cost_type, sad_per_bit, error_per_bit, invert_mask;
   const int32_t *mvjcost, *mvcost0, *mvcost1;
-};
-
-__device__ __forceinline__ int64_t wsum(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor((long long)v, m, 64);
-  return v;
-}
-__device__ __forceinline__ int mv_bits(const CompoundArgs &a, int dr, int dc) {
-  return a.mvjcost[(dc != 0) | ((dr != 0) << 1)] + a.mvcost0[dr] + a.mvcost1[dc];
-}
-__device__ __forceinline__ int sad_cost(const CompoundArgs &a, int frr, int frc, int row, int col) {   // mvsad_err_cost_ (:310-339)
-  const int dr = (row - frr) * 8, dc = (col - frc) * 8;
-  if (a.cost_type == kCostEntropy) return (int)(((unsigned)mv_bits(a, dr, dc) * (unsigned)a.sad_per_bit + 256u) >> 9);
-  const int lambda = a.cost_type == kCostL1Low ? 32 : a.cost_type == kCostL1Mid ? 15 : a.cost_type == kCostL1Hd ? 8 : 0;
-  return (lambda * (iabsm(dr) + iabsm(dc))) >> 3;
-}
-// the same with what does not depend on the candidate worked out once per block (left inline the compiler re-derived lambda from cost_type
-// through a chain of scalar branches at every call)
-struct SadCost {
-  const CompoundArgs &a;
-  int frr, frc, lambda;
-  bool entropy;
-  __device__ __forceinline__ SadCost(const CompoundArgs &a_, int frr_, int frc_) : a(a_), frr(frr_), frc(frc_) {
-    entropy = a.cost_type == kCostEntropy;
-    lambda = a.cost_type == kCostL1Low ? 32 : a.cost_type == kCostL1Mid ? 15 : a.cost_type == kCostL1Hd ? 8 : 0;
-  }
-  __device__ __forceinline__ int operator()(int row, int col) const {
-    const int dr = (row - frr) * 8, dc = (col - frc) * 8;
-    if (entropy) return (int)(((unsigned)mv_bits(a, dr, dc) * (unsigned)a.sad_per_bit + 256u) >> 9);
-    return (lambda * (iabsm(dr) + iabsm(dc))) >> 3;
+  __device__ __forceinline__ MvCost<> cost(int ref_row, int ref_col) const {   // the MV cost of one block's search
+    return MvCost<>(cost_type, ref_row, ref_col, sad_per_bit, error_per_bit, mvjcost, mvcost0, mvcost1);
   }
 };
-__device__ __forceinline__ int var_cost(const CompoundArgs &a, int ref_row, int ref_col, int mrow, int mcol) {   // mv_err_cost_ (:271-308)
-  const int dr = mrow - ref_row, dc = mcol - ref_col;
-  if (a.cost_type == kCostEntropy) return (int)(((int64_t)mv_bits(a, dr, dc) * a.error_per_bit + (1 << 13)) >> 14);
-  const int lambda = a.cost_type == kCostL1Low ? 2 : a.cost_type == kCostL1Hd ? 1 : 0;
-  return (lambda * (iabsm(dr) + iabsm(dc))) >> 3;
-}
-__device__ __forceinline__ uint32_t finish_var(int64_t s64, uint64_t q64, int n_px, int bit_depth) {   // variance.c:141-148 / :383-420
-  int32_t s;
-  uint32_t q;
-  if (bit_depth == 10) { q = (uint32_t)((q64 + 8) >> 4); s = (int32_t)((s64 + 2) >> 2); }
-  else if (bit_depth == 12) { q = (uint32_t)((q64 + 128) >> 8); s = (int32_t)((s64 + 8) >> 4); }
-  else { q = (uint32_t)q64; s = (int32_t)s64; }
-  const int64_t sq = ((int64_t)s * s) >> __builtin_ctz((unsigned)n_px);   // (/ (w * h): block areas are powers of two -- a 64-bit division is ~100 instructions)
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0u;
-}
 
-// 32-bit sum over the wavefront, wave-uniform result: four DPP steps to the sums of the four 16-lane rows, four v_readlane, scalar adds
-__device__ __forceinline__ uint32_t row_sum32(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);    // quad_perm [1, 0, 3, 2]
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, false);    // quad_perm [2, 3, 0, 1]
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xf, 0xf, false);   // row_half_mirror
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xf, 0xf, false);   // row_mirror
-  return v;
-}
-// the four 16-lane sums of row_sum32 added up: row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3, the total in lane 63 -- two DPP
-// adds and one v_readlane instead of four v_readlane and three s_add (these kernels are bound by the CU's one scalar unit, PMC r05e)
-__device__ __forceinline__ uint32_t rows_total32(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast15
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast31
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t wsum32(uint32_t v) { return rows_total32(row_sum32(v)); }
-__device__ __forceinline__ uint64_t wsum32_wide(uint32_t v) {   // the same when only the row sums fit 32 bits
-  v = row_sum32(v);
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) + (uint32_t)__builtin_amdgcn_readlane((int)v, 32) +
-         (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-}
-// The sums of the variance's two accumulators over the wavefront without the six dependent 64-bit shuffle steps of wsum(): the sum of
+// 32-bit sum over the wavefront, wave-uniform result: four DPP steps to the sums of the four 16-lane rows, then rows_total32 (search_device.h)
+__device__ __forceinline__ uint32_t wsum32(uint32_t v) { return rows_total32(row16_sum(v)); }
+// The sums of the variance's two accumulators over the wavefront without the six dependent 64-bit shuffle steps of wave_sum64(): the sum of
 // differences fits 32 bits (|d| <= 8191, <= 128 x 128 pixels), the sum of squares is summed as its low 16 bits and the rest (a lane's
 // share is < 2^42: <= 256 pixels of d^2 < 2^26) -- DPP adds only.
 __device__ __forceinline__ int64_t wsum_s(int64_t s) { return (int64_t)(int32_t)wsum32((uint32_t)(int32_t)s); }
@@ -320,7 +256,7 @@ template <typename T, int UNITS, int G = 1, bool PACKED = true> struct CompoundE
     return acc;
   }
   // G candidates at once: rows = sad_rows(offset per group), then sad_of(rows, g) for each
-  __device__ __forceinline__ uint32_t sad_rows(unsigned off, const Px &px) const { return row_sum32(sad_partial(off, px)); }
+  __device__ __forceinline__ uint32_t sad_rows(unsigned off, const Px &px) const { return row16_sum(sad_partial(off, px)); }
   __device__ __forceinline__ uint32_t sad_rows(unsigned off) const {
     Px px;
     fetch(off, px);
@@ -339,8 +275,8 @@ template <typename T, int UNITS, int G = 1, bool PACKED = true> struct CompoundE
 #pragma unroll
       for (int k = 0; k < kUnits; ++k)
         if (kFull || k * 4 * kLanes < n_px) unit_var(f2[k], sA_[k], sC_[k], sS_[k], s, q);
-      if constexpr (G == 1) q64 = wsum32_wide(q);
-      else q64 = group_total(row_sum32(q), 0);   // (every group evaluated the same candidate; <= 128 pixels: 32 bits)
+      if constexpr (G == 1) q64 = rows_total64(row16_sum(q));
+      else q64 = group_total(row16_sum(q), 0);   // (every group evaluated the same candidate; <= 128 pixels: 32 bits)
     } else if constexpr (G > 1) {
       q64 = 0;
     } else {
@@ -354,7 +290,8 @@ template <typename T, int UNITS, int G = 1, bool PACKED = true> struct CompoundE
       }
       q64 = wsum_q(q);
     }
-    return finish_var((int64_t)(int32_t)group_total(row_sum32((uint32_t)s), 0), q64, n_px, bit_depth);
+    uint32_t sse;
+    return finish_var((int64_t)(int32_t)group_total(row16_sum((uint32_t)s), 0), q64, bit_depth, __builtin_ctz((unsigned)n_px), &sse);   // (block areas are powers of two)
   }
 };
 
@@ -374,8 +311,7 @@ __global__ __launch_bounds__(256) void refining_search_8p_kernel(PlaneView<T> sr
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)by * ref.stride + bx;
   const T *pred = second_pred + (size_t)bi * n_px;
   const uint8_t *mask = masks ? masks + (size_t)bi * n_px : nullptr;
-  const int frr = (bs.ref_row + 3 + (bs.ref_row >= 0)) >> 3, frc = (bs.ref_col + 3 + (bs.ref_col >= 0)) >> 3;
-  const SadCost cost_of(a, frr, frc);   // mvsad_err_cost_
+  const MvCost<> mc = a.cost(bs.ref_row, bs.ref_col);
   CompoundEval<T, UNITS, G, PACKED> ce;
   ce.init(sp, src.stride, rbase, ref.stride, pred, mask, W, H, a.invert_mask, a.bit_depth, lane, bs.row_min, bs.col_min);
   auto sad_at = [&](int row, int col) -> uint32_t { return ce.sad(row, col); };   // get_mvpred_compound_sad
@@ -383,7 +319,7 @@ __global__ __launch_bounds__(256) void refining_search_8p_kernel(PlaneView<T> sr
   unsigned long long visited = 0;                       // the 49 cells of do_refine_search_grid
   int grid_center = kRange * kStride + kRange;
   int row = min(max(bs.start_row, bs.row_min), bs.row_max), col = min(max(bs.start_col, bs.col_min), bs.col_max);   // clamp_fullmv
-  uint32_t best_sad = sad_at(row, col) + (uint32_t)cost_of(row, col);
+  uint32_t best_sad = sad_at(row, col) + (uint32_t)mc.sad(row, col);
   visited |= 1ull << grid_center;
   // neighbors[] (:1623-1632): (-1,0) (0,-1) (0,1) (1,0) (-1,-1) (1,-1) (-1,1) (1,1)
   auto drow_of = [](int j) { return j == 0 || j == 4 || j == 6 ? -1 : (j == 3 || j == 5 || j == 7 ? 1 : 0); };
@@ -405,7 +341,7 @@ __global__ __launch_bounds__(256) void refining_search_8p_kernel(PlaneView<T> sr
         [&](int j, uint32_t rows, int g) {
           uint32_t sad = ce.sad_of(rows, g);
           if (sad < best_sad) {
-            sad += (uint32_t)cost_of(row + drow_of(j), col + dcol_of(j));
+            sad += (uint32_t)mc.sad(row + drow_of(j), col + dcol_of(j));
             if (sad < best_sad) {
               best_sad = sad;
               best_site = j;
@@ -420,7 +356,7 @@ __global__ __launch_bounds__(256) void refining_search_8p_kernel(PlaneView<T> sr
     grid_center += drow * kStride + dcol;
   }
   // av1_get_mvpred_compound_var: svaf / msvf at sub-pel offset (0, 0) -- the bilinear passes with offset 0 are the identity -- + mv_err_cost_
-  const int var = (int)ce.var(row, col) + var_cost(a, bs.ref_row, bs.ref_col, row * 8, col * 8);
+  const int var = (int)ce.var(row, col) + mc.var(row * 8, col * 8);
   if (lane == 0) {
     out_mv[2 * bi] = (int16_t)row; out_mv[2 * bi + 1] = (int16_t)col;
     out_sad[bi] = (int32_t)best_sad;
@@ -457,16 +393,15 @@ __global__ __launch_bounds__(256) void compound_full_pixel_diamond_kernel(PlaneV
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)by * ref.stride + bx;
   const T *pred = second_pred + (size_t)bi * n_px;
   const uint8_t *mask = masks ? masks + (size_t)bi * n_px : nullptr;
-  const int frr = (bs.ref_row + 3 + (bs.ref_row >= 0)) >> 3, frc = (bs.ref_col + 3 + (bs.ref_col >= 0)) >> 3;
-  const SadCost cost_of(a, frr, frc);   // mvsad_err_cost_
+  const MvCost<> mc = a.cost(bs.ref_row, bs.ref_col);
   CompoundEval<T, UNITS, G, PACKED> ce;
   ce.init(sp, src.stride, rbase, ref.stride, pred, mask, W, H, a.invert_mask, a.bit_depth, lane, bs.row_min, bs.col_min);
   auto sad_at = [&](int row, int col) -> uint32_t { return ce.sad(row, col); };   // get_mvpred_compound_sad: sdaf / msdf
   auto var_at = [&](int row, int col) -> int {   // get_mvpred_compound_var_cost: svaf / msvf at offset (0, 0) + mv_err_cost_
-    return (int)ce.var(row, col) + var_cost(a, bs.ref_row, bs.ref_col, row * 8, col * 8);
+    return (int)ce.var(row, col) + mc.var(row * 8, col * 8);
   };
   const int start_row = min(max(bs.start_row, bs.row_min), bs.row_max), start_col = min(max(bs.start_col, bs.col_min), bs.col_max);   // clamp_fullmv
-  const uint32_t start_sad = sad_at(start_row, start_col) + (uint32_t)cost_of(start_row, start_col);   // (the same in every run)
+  const uint32_t start_sad = sad_at(start_row, start_col) + (uint32_t)mc.sad(start_row, start_col);   // (the same in every run)
   int second_row = -32768, second_col = -32768;   // MARK_MV_INVALID (av1_full_pixel_search, :1704-1707)
   const int nsteps = __builtin_amdgcn_readfirstlane(S.num_search_steps);
   auto diamond = [&](int search_step, int *num00, int *orow, int *ocol) -> int {
@@ -499,7 +434,7 @@ __global__ __launch_bounds__(256) void compound_full_pixel_diamond_kernel(PlaneV
             if (sad < bestsad) {
               const int site = __builtin_amdgcn_readlane(my_site, idx);
               // (the cost is looked up only for a site that can win: issuing it for every site beside the pixel reads was SLOWER, 7.7 -> 8.9 ms)
-              sad += (uint32_t)cost_of(row + (int)(int16_t)(site & 0xffff), col + (site >> 16));
+              sad += (uint32_t)mc.sad(row + (int)(int16_t)(site & 0xffff), col + (site >> 16));
               if (sad < bestsad) {
                 bestsad = sad;
                 best_site = idx;
@@ -573,8 +508,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)by * ref.stride + bx;
   const int32_t *wsrc = wsrc_all + (size_t)bi * n_px, *omask = omask_all + (size_t)bi * n_px;
   const int shift = a.bit_depth == 10 ? 2 : a.bit_depth == 12 ? 4 : 0;
-  const int frr = (bs.ref_row + 3 + (bs.ref_row >= 0)) >> 3, frc = (bs.ref_col + 3 + (bs.ref_col >= 0)) >> 3;
-  const SadCost cost_of(a, frr, frc);   // mvsad_err_cost_
+  const MvCost<> mc = a.cost(bs.ref_row, bs.ref_col);
   // As CompoundEval: the weighted source and the mask of the block stay in registers for blocks of up to 256 * UNITS pixels, a candidate is then
   // 2 * UNITS independent reference loads per lane; larger blocks stream them four pixels at a time.  Widths are powers of two (row / column
   // of pixel t by shift and mask).
@@ -647,7 +581,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
     }
     return acc;
   };
-  auto osad_rows = [&](unsigned off, const Px &px) -> uint32_t { return row_sum32(osad_partial(off, px)); };
+  auto osad_rows = [&](unsigned off, const Px &px) -> uint32_t { return row16_sum(osad_partial(off, px)); };
   auto osad_of = [&](uint32_t rows, int g) -> uint32_t { return CompoundEval<T, UNITS, G>::group_total(rows, g) >> shift; };   // + the bit-depth wrapper
   auto osad_at = [&](int row, int col) -> uint32_t {
     Px px;
@@ -671,7 +605,8 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
         q += (uint32_t)(d * d);
       }
     }
-    return (int)finish_var(wsum_s(s), wsum_q((uint64_t)q), n_px, a.bit_depth) + var_cost(a, bs.ref_row, bs.ref_col, row * 8, col * 8);
+    uint32_t sse;
+    return (int)finish_var(wsum_s(s), wsum_q((uint64_t)q), a.bit_depth, __builtin_ctz((unsigned)n_px), &sse) + mc.var(row * 8, col * 8);
   };
   auto in_range = [&](int r, int c) { return c >= bs.col_min && c <= bs.col_max && r >= bs.row_min && r <= bs.row_max; };
   const int start_row = min(max(bs.start_row, bs.row_min), bs.row_max), start_col = min(max(bs.start_col, bs.col_min), bs.col_max);
@@ -682,7 +617,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
       const int tot_steps = nsteps - search_step;   // (table reads through v_readfirstlane / v_readlane: see compound_full_pixel_diamond_kernel)
       int row = start_row, col = start_col;
       *num00 = 0;
-      int best_sad = (int)(osad_at(row, col) + (uint32_t)cost_of(row, col));
+      int best_sad = (int)(osad_at(row, col) + (uint32_t)mc.sad(row, col));
       for (int step = tot_steps - 1; step >= 0; --step) {
         int best_site = 0;
         const int nper = __builtin_amdgcn_readfirstlane(S.searches_per_step[step]);
@@ -696,7 +631,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
           int sad = (int)osad_of(rows, g);   // (`int sad < int best_sad`: this function compares signed, mcomp.c:2206-2215)
           if (sad < best_sad) {
             const int site = __builtin_amdgcn_readlane(my_site, idx);
-            sad += cost_of(row + (int)(int16_t)(site & 0xffff), col + (site >> 16));
+            sad += mc.sad(row + (int)(int16_t)(site & 0xffff), col + (site >> 16));
             if (sad < best_sad) {
               best_sad = sad;
               best_site = idx;
@@ -735,7 +670,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
     result = bestsme;
   } else {   // obmc_refining_search_sad from the clamped start MV
     int row = start_row, col = start_col;
-    uint32_t best_sad = osad_at(row, col) + (uint32_t)cost_of(row, col);
+    uint32_t best_sad = osad_at(row, col) + (uint32_t)mc.sad(row, col);
     for (int i = 0; i < 8; ++i) {
       int best_site = -1;
       // neighbors[4] = (-1,0) (0,-1) (0,1) (1,0), one per lane
@@ -744,7 +679,7 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
       walk_sites<G, Px>((uint32_t)__ballot(ok_l), ok_l ? cand_off(r_l, c_l) : 0u, 0u, grp, ofetch, osad_rows, [&](int j, uint32_t rows, int g) {
         uint32_t sad = osad_of(rows, g);
         if (sad < best_sad) {
-          sad += (uint32_t)cost_of(row + (j == 0 ? -1 : j == 3 ? 1 : 0), col + (j == 1 ? -1 : j == 2 ? 1 : 0));
+          sad += (uint32_t)mc.sad(row + (j == 0 ? -1 : j == 3 ? 1 : 0), col + (j == 1 ? -1 : j == 2 ? 1 : 0));
           if (sad < best_sad) {
             best_sad = sad;
             best_site = j;
@@ -805,6 +740,7 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
   const int bi = blockIdx.x * 4 + wave;
   if (bi >= n_blocks) return;
   const BlockScalars bs = BlockScalars::of(blocks[bi]);   // start_* in 1/8 pel, limits = SubpelMvLimits
+  const MvCost<> mc = a.cost(bs.ref_row, bs.ref_col);
   const int bx = __builtin_amdgcn_readfirstlane((int)blocks[bi].bx), by = __builtin_amdgcn_readfirstlane((int)blocks[bi].by);
   const int W = a.bw, H = a.bh, n_px = W * H;
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)by * ref.stride + bx;
@@ -963,15 +899,11 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
       s += d;
       q += (uint32_t)(d * d);
     }
-    const int64_t s64 = wsum_s(s);
-    const uint64_t q64 = wsum_q((uint64_t)q);
-    *sse_out = a.bit_depth == 10 ? (uint32_t)((q64 + 8) >> 4) : a.bit_depth == 12 ? (uint32_t)((q64 + 128) >> 8) : (uint32_t)q64;
-    return finish_var(s64, q64, n_px, a.bit_depth);
+    return finish_var(wsum_s(s), wsum_q((uint64_t)q), a.bit_depth, __builtin_ctz((unsigned)n_px), sse_out);
   };
   auto est_cost = [&](int mrow, int mcol) -> uint32_t {   // estimate_obmc_mvcost: the difference x 8 (GET_MV_SUBPEL), 13-bit rounding; 0 but for ENTROPY
-    if (a.cost_type != kCostEntropy) return 0u;
-    const int dr = (mrow - bs.ref_row) * 8, dc = (mcol - bs.ref_col) * 8;
-    return ((unsigned)mv_bits(a, dr, dc) * (unsigned)a.error_per_bit + 4096u) >> 13;
+    if (!mc.entropy) return 0u;
+    return ((unsigned)mc.bits((mrow - bs.ref_row) * 8, (mcol - bs.ref_col) * 8) * (unsigned)a.error_per_bit + 4096u) >> 13;
   };
   uint32_t besterr, sse1;
   int distortion, best_row = bs.start_row, best_col = bs.start_col;
@@ -979,13 +911,13 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
     uint32_t q;
     const uint32_t v = sa.upsampled ? obmc_err(best_row, best_col, 2, &q) : obmc_err(0, 0, 0, &q);
     distortion = (int)v; sse1 = q;
-    besterr = v + (uint32_t)var_cost(a, bs.ref_row, bs.ref_col, best_row, best_col);
+    besterr = v + (uint32_t)mc.var(best_row, best_col);
   }
   auto check = [&](int mrow, int mcol, int *has_better) -> uint32_t {   // obmc_check_better / obmc_check_better_fast
     if (mcol < bs.col_min || mcol > bs.col_max || mrow < bs.row_min || mrow > bs.row_max) return (uint32_t)INT_MAX;
     uint32_t q;
     const int thismse = (int)obmc_err(mrow, mcol, sa.upsampled ? 2 : 1, &q);
-    uint32_t cost = sa.upsampled ? (uint32_t)var_cost(a, bs.ref_row, bs.ref_col, mrow, mcol) : est_cost(mrow, mcol);
+    uint32_t cost = sa.upsampled ? (uint32_t)mc.var(mrow, mcol) : est_cost(mrow, mcol);
     cost += (uint32_t)thismse;
     if (cost < besterr) {
       besterr = cost; best_row = mrow; best_col = mcol; distortion = thismse; sse1 = q;

@@ -114,13 +114,9 @@ __global__ __launch_bounds__(256) void block_var_kernel(PlaneView<T> src, int sr
   long long sum;
   const unsigned long long sse = wave_block_sse(s, src.stride, p, pred.stride, bw, bh, lane, &sum);
   if (lane == 0) {
-    const uint32_t q = depth_sse(sse, bit_depth);
-    const int32_t sm = bit_depth == 10 ? (int32_t)((sum + 2) >> 2) : bit_depth == 12 ? (int32_t)((sum + 8) >> 4) : (int32_t)sum;
-    const int64_t sq = ((int64_t)sm * sm) / (bw * bh);
-    out_sse[i] = q;
-    if (!out_var) return;
-    if (bit_depth == 8) out_var[i] = q - (uint32_t)sq;
-    else { const int64_t v = (int64_t)q - sq; out_var[i] = v >= 0 ? (uint32_t)v : 0u; }
+    uint32_t v;
+    finish(sum, sse, bit_depth, __builtin_ctz((unsigned)(bw * bh)), &v, &out_sse[i]);   // (block areas are powers of two: the division by bw * bh is a shift)
+    if (out_var) out_var[i] = v;
   }
 }
 }  // namespace
@@ -263,19 +259,19 @@ __global__ void single_finish_kernel(const aomhip_search_block *blocks, const in
   }
   if (full_mv[2 * i] != kInvalidMv) {
     const aomhip_search_block b = blocks[i];
-    auto mv_rate = [&](int r, int c) { return mv_bit_cost(mvjcost, mvcost0, mvcost1, r - b.ref_row, c - b.ref_col); };   // av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266)
+    auto rate_of = [&](int r, int c) { return mv_rate(mvjcost, mvcost0, mvcost1, r - b.ref_row, c - b.ref_col); };   // av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266)
     if (force_integer_mv) { row = full_mv[2 * i] * 8; col = full_mv[2 * i + 1] * 8; }   // convert_fullmv_to_mv (:343-345)
     else {
       row = mv_a[2 * i]; col = mv_a[2 * i + 1]; sse = sse_a[i];
       if (yrd_a) {
         if (has_second[i]) {   // RDCOST(x->rdmult, mv_rate + stats.rate, stats.dist) of both; the second one replaces the first when SMALLER (:414-418)
-          const int64_t rd = ((((int64_t)mv_rate(row, col) + yrd_a[i].rate) * rdmult + 256) >> 9) + yrd_a[i].dist * 128;
-          const int64_t tmp_rd = ((((int64_t)yrd_b[i].rate + mv_rate(mv_b[2 * i], mv_b[2 * i + 1])) * rdmult + 256) >> 9) + yrd_b[i].dist * 128;
+          const int64_t rd = ((((int64_t)rate_of(row, col) + yrd_a[i].rate) * rdmult + 256) >> 9) + yrd_a[i].dist * 128;
+          const int64_t tmp_rd = ((((int64_t)yrd_b[i].rate + rate_of(mv_b[2 * i], mv_b[2 * i + 1])) * rdmult + 256) >> 9) + yrd_b[i].dist * 128;
           if (tmp_rd < rd) { row = mv_b[2 * i]; col = mv_b[2 * i + 1]; sse = sse_b[i]; }
         }
       } else if (mv_b && (int)err_b[i] < (int)err_a[i]) { row = mv_b[2 * i]; col = mv_b[2 * i + 1]; sse = sse_b[i]; }   // this_var < best_mv_var (:421-425)
     }
-    rate = mv_rate(row, col);
+    rate = rate_of(row, col);
   }
   best_mv[2 * i] = (int16_t)row; best_mv[2 * i + 1] = (int16_t)col;
   rate_mv[i] = rate;

@@ -285,11 +285,6 @@ static int launch_x4d(const SadLaunch &l, const PlaneView<T> &s, const PlaneView
   return launch_x4d_v<T, W, H, SKIP, 0>(l, s, r, g, n, gfs, out);
 }
 
-// Dispatch over the reference's 22 block sizes (av1/common/enums.h:99-124).
-#define AOMHIP_FOR_BLOCK_SIZES(X)                                                                                \
-  X(4, 4) X(4, 8) X(8, 4) X(8, 8) X(8, 16) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32) X(32, 64) X(64, 32) \
-  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
-
 template <typename T, typename CandT>
 static int dispatch(bool x4d, const SadLaunch &l, const PlaneView<T> &s, const PlaneView<T> &r, int bw, int bh,
                     const CandT *c, int n, int64_t cfs, uint32_t *out) {

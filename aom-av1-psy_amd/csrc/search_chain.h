@@ -12,8 +12,6 @@ namespace aomhip {
 constexpr int kMaxFullPel = 1023;          // MAX_FULL_PEL_VAL (mcomp_structs.h:22)
 constexpr int kMvLow = -(1 << 14), kMvUpp = 1 << 14;  // MV_LOW / MV_UPP (entropymv.h:75-76)
 
-__device__ __forceinline__ int rawpel(int x) { return (x + 3 + (x >= 0)) >> 3; }  // GET_MV_RAWPEL (mv.h:28)
-
 // FullMvLimits: av1_set_mv_search_range(&limits, &ref_mv) (mcomp.c:196-215) on the raw x->mv_limits `b` holds (an aomhip_search_block or its
 // BlockScalars); ref_mv in 1/8 pel, kZeroMv for the searches around the zero baseline (+-1023 then)
 template <typename B> __device__ __forceinline__ void full_limits(B &b, int ref_row, int ref_col) {
@@ -65,14 +63,8 @@ __device__ __forceinline__ unsigned long long wave_block_sse(const T *s, int sst
     const int d = (int)s[(int64_t)y * sstride + x] - (int)p[(int64_t)y * pstride + x];
     sum += d; sse += (unsigned)__mul24(d, d);
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) { sum += __shfl_xor(sum, m, 64); sse += __shfl_xor(sse, m, 64); }
-  *sum_out = sum;
-  return sse;
-}
-// the sse of the mse / variance functions at a bit depth (aom_dsp/variance.c:383-420 HIGHBD_VAR: ROUND_POWER_OF_TWO(sse, 4 or 8))
-__device__ __forceinline__ uint32_t depth_sse(unsigned long long sse, int bit_depth) {
-  return bit_depth == 10 ? (uint32_t)((sse + 8) >> 4) : bit_depth == 12 ? (uint32_t)((sse + 128) >> 8) : (uint32_t)sse;
+  *sum_out = wave_sum64(sum);
+  return (unsigned long long)wave_sum64((int64_t)sse);
 }
 
 // fn_ptr[bsize].vf(src, pred) (aom_dsp/variance.c:141-148 VAR, :383-420 HIGHBD_VAR) of every block at its own position in both planes; d_var may be

@@ -1,11 +1,19 @@
-// Device helpers shared by the motion-search kernels (mcomp.hip, fullpel_search.hip): 8-lanes-per-candidate SAD,
-// 16-lanes-per-candidate (sub-pel) variance, the L1 / NONE MV cost forms.  Not part of the ABI.
+// Device helpers shared by the motion-search kernels (mcomp.hip, mcomp_compound.hip, fullpel_search.inc, subpel_search.inc, warp_refine.hip and
+// the composites over them).  What lives here, once:
+//   rawpel() / MvCost   GET_MV_RAWPEL and the MV cost of a search (mvsad_err_cost_, mv_err_cost_, av1_mv_bit_cost; the two lambda tables)
+//   row8_sum / row16_sum / rows_total32 / rows_total64 / wave_sum64   the sums over 8 lanes, a DPP row, the four rows, the wavefront
+//   group8_sad*          the 8-lanes-per-candidate SAD (plane, uniform base, LDS window)
+//   wave_variance / group16_variance   the (sub-pel) variance by 64 / 16 lanes; their tail is finish_var of variance_finish.h, which the
+//                        variance kernels share (variance_device.h)
+//   CompoundRef          the other predictor of a compound search
+// Not part of the ABI.
 #ifndef AOMHIP_CSRC_SEARCH_DEVICE_H_
 #define AOMHIP_CSRC_SEARCH_DEVICE_H_
 
 #include <climits>
 
 #include "common.h"
+#include "variance_finish.h"
 
 namespace aomhip {
 
@@ -23,32 +31,95 @@ constexpr int kInvalidMv = -32768;  // INVALID_MV_ROW_COL (av1/common/mv.h:27)
 
 __device__ __forceinline__ int iabsm(int v) { return v < 0 ? -v : v; }
 
-struct CostCtx {
-  int cost_type, ref_row, ref_col;  // ref_mv in 1/8 pel
-  __device__ __forceinline__ int sad_cost(int row, int col) const {  // mvsad_err_cost_ (mcomp.c:310-339)
-    const int frr = (ref_row + 3 + (ref_row >= 0)) >> 3, frc = (ref_col + 3 + (ref_col >= 0)) >> 3;  // GET_MV_RAWPEL
-    const int d = iabsm((row - frr) * 8) + iabsm((col - frc) * 8);
-    const int lambda = cost_type == kCostL1Low ? 32 : cost_type == kCostL1Mid ? 15 : cost_type == kCostL1Hd ? 8 : 0;
-    return (lambda * d) >> 3;
+__device__ __forceinline__ int rawpel(int x) { return (x + 3 + (x >= 0)) >> 3; }  // GET_MV_RAWPEL (mv.h:28)
+
+// mv_cost (mcomp.c:249-258) of the difference (dr, dc) to ref_mv in 1/8 pel: joint + the two component tables, addressed from their centres
+__device__ __forceinline__ int mv_bits(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
+  return mvjcost[(dc != 0) | ((dr != 0) << 1)] + mvcost0[dr] + mvcost1[dc];
+}
+
+// ... as the rate of a result: av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266), ROUND_POWER_OF_TWO(bits * 108, 7)
+__device__ __forceinline__ int mv_rate(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
+  return (int)(((int64_t)mv_bits(mvjcost, mvcost0, mvcost1, dr, dc) * 108 + 64) >> 7);
+}
+
+// The MV cost of one block's search, built once per block: what the SAD stage needs per candidate -- ref_mv's full-pel form, its lambda, whether
+// the tables apply -- is worked out here (derived at every call, the compiler re-derived lambda from cost_type through a chain of scalar
+// branches per candidate).  The variance stage's lambda is derived where it is used: held in a scalar register for the whole search it took
+// the 8-bit sub-pel and the four-candidate compound kernels from 100 to 102 SGPRs, 8 -> 7 wavefronts per SIMD.  TABLES = false compiles the MV_COST_ENTROPY path out, for kernels
+// whose entry points reject it (check_common).  A kernel whose search state has to stay on the scalar unit wraps frr / frc in
+// v_readfirstlane after construction (mcomp.hip).
+template <bool TABLES = true> struct MvCost {
+  int cost_type;
+  bool entropy;           // MV_COST_ENTROPY: the caller's tables
+  int ref_row, ref_col;   // ref_mv in 1/8 pel
+  int frr, frc;           // ... in full pel: get_fullmv_from_mv
+  int lambda_sad;         // mvsad_err_cost_ of the L1 types (mcomp.c:310-339): LOWRES 32, MIDRES 15, HDRES 8
+  int sad_per_bit, error_per_bit;
+  const int32_t *mvjcost, *mvcost0, *mvcost1;
+  __device__ __forceinline__ MvCost(int cost_type_, int ref_row_, int ref_col_, int sad_per_bit_ = 0, int error_per_bit_ = 0, const int32_t *mvjcost_ = nullptr,
+                                    const int32_t *mvcost0_ = nullptr, const int32_t *mvcost1_ = nullptr)
+      : cost_type(cost_type_), entropy(TABLES && cost_type_ == kCostEntropy), ref_row(ref_row_), ref_col(ref_col_), frr(rawpel(ref_row_)), frc(rawpel(ref_col_)),
+        lambda_sad(cost_type_ == kCostL1Low ? 32 : cost_type_ == kCostL1Mid ? 15 : cost_type_ == kCostL1Hd ? 8 : 0), sad_per_bit(sad_per_bit_),
+        error_per_bit(error_per_bit_), mvjcost(mvjcost_), mvcost0(mvcost0_), mvcost1(mvcost1_) {}
+  __device__ __forceinline__ int bits(int dr, int dc) const { return mv_bits(mvjcost, mvcost0, mvcost1, dr, dc); }
+  // mvsad_err_cost_ of the full-pel MV (row, col): ROUND_POWER_OF_TWO((unsigned)bits * sad_per_bit, 9), or (lambda * 8 d) >> 3 = lambda * d
+  __device__ __forceinline__ int sad(int row, int col) const {
+    if (TABLES && entropy) return (int)(((unsigned)bits((row - frr) * 8, (col - frc) * 8) * (unsigned)sad_per_bit + 256u) >> 9);
+    return lambda_sad * (iabsm(row - frr) + iabsm(col - frc));
   }
-  __device__ __forceinline__ int var_cost(int mrow, int mcol) const {  // mv_err_cost_ (mcomp.c:271-308)
-    const int d = iabsm(mrow - ref_row) + iabsm(mcol - ref_col);
+  // mv_err_cost_ of the MV (mrow, mcol) in 1/8 pel (:271-308): ROUND_POWER_OF_TWO_64((int64)bits * error_per_bit, 14), or (lambda * d) >> 3 with
+  // lambda 2 / 0 / 1 for LOWRES / MIDRES / HDRES
+  __device__ __forceinline__ int var(int mrow, int mcol) const {
+    const int dr = mrow - ref_row, dc = mcol - ref_col;
+    if (TABLES && entropy) return (int)(((int64_t)bits(dr, dc) * error_per_bit + (1 << 13)) >> 14);
     const int lambda = cost_type == kCostL1Low ? 2 : cost_type == kCostL1Mid ? 0 : cost_type == kCostL1Hd ? 1 : 0;
-    return (lambda * d) >> 3;
+    return (lambda * (iabsm(dr) + iabsm(dc))) >> 3;
   }
+  // the rate of a result: av1_mv_bit_cost(.., MV_COST_WEIGHT)
+  __device__ __forceinline__ int rate(int mrow, int mcol) const { return mv_rate(mvjcost, mvcost0, mvcost1, mrow - ref_row, mcol - ref_col); }
 };
 
-// MV_COST_ENTROPY: mv_cost (mcomp.c:249-258) of the difference (dr, dc) to ref_mv in 1/8 pel, from the caller's cost tables ...
-__device__ __forceinline__ int64_t mv_joint_bits(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
-  return (int64_t)mvjcost[(dc != 0) | ((dr != 0) << 1)] + mvcost0[dr] + mvcost1[dc];
+// Sums of a 32- or 64-bit value over lanes, by DPP inside the 16-lane rows (no LDS, no cross-row traffic): row_lane<CTRL> is the value of the
+// lane CTRL names (0xB1 quad_perm [1,0,3,2], 0x4E quad_perm [2,3,0,1], 0x141 row_half_mirror, 0x140 row_mirror).  row8_sum: every lane gets
+// the sum of its group of 8; row16_sum: of its row.
+template <int CTRL, typename V> __device__ __forceinline__ V row_lane(V v) {
+  if constexpr (sizeof(V) == 8) {
+    const uint32_t lo = __builtin_amdgcn_update_dpp(0u, (uint32_t)v, CTRL, 0xf, 0xf, false);
+    const uint32_t hi = __builtin_amdgcn_update_dpp(0u, (uint32_t)((uint64_t)v >> 32), CTRL, 0xf, 0xf, false);
+    return (V)(((uint64_t)hi << 32) | lo);
+  } else {
+    return (V)__builtin_amdgcn_update_dpp(0u, (uint32_t)v, CTRL, 0xf, 0xf, false);
+  }
 }
-// ... as mv_err_cost_ weighs it (mcomp.c:271-308): ROUND_POWER_OF_TWO_64(bits * error_per_bit, 14) ...
-__device__ __forceinline__ int mv_err_cost_bits(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc, int error_per_bit) {
-  return (int)((mv_joint_bits(mvjcost, mvcost0, mvcost1, dr, dc) * error_per_bit + (1 << 13)) >> 14);
+template <typename V> __device__ __forceinline__ V row8_sum(V v) {
+  v += row_lane<0xB1>(v);
+  v += row_lane<0x4E>(v);
+  v += row_lane<0x141>(v);
+  return v;
 }
-// ... and as the rate of a result: av1_mv_bit_cost(.., MV_COST_WEIGHT) (mcomp.c:261-266), ROUND_POWER_OF_TWO(bits * 108, 7)
-__device__ __forceinline__ int mv_bit_cost(const int32_t *mvjcost, const int32_t *mvcost0, const int32_t *mvcost1, int dr, int dc) {
-  return (int)((mv_joint_bits(mvjcost, mvcost0, mvcost1, dr, dc) * 108 + 64) >> 7);
+template <typename V> __device__ __forceinline__ V row16_sum(V v) {
+  v = row8_sum(v);
+  v += row_lane<0x140>(v);
+  return v;
+}
+// The four row sums of row16_sum added up, wave-uniform: row_bcast15 into rows 1 and 3, row_bcast31 into rows 2 and 3, the total in lane 63 -- two
+// DPP adds and one v_readlane instead of four v_readlane and three s_add (the compound searches are bound by the CU's one scalar unit, PMC r05e)
+__device__ __forceinline__ uint32_t rows_total32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast15
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast31
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+// ... when only the row sums fit 32 bits: four v_readlane, 64-bit scalar adds
+__device__ __forceinline__ uint64_t rows_total64(uint32_t v) {
+  return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)v, 0) + (uint32_t)__builtin_amdgcn_readlane((int)v, 16) + (uint32_t)__builtin_amdgcn_readlane((int)v, 32) +
+         (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+}
+// a 64-bit value over the wavefront, every lane gets the sum: six shuffle steps
+__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor((long long)v, m, 64);
+  return v;
 }
 
 #ifndef AOMHIP_SEARCH_ALIGNED_LOADS
@@ -164,10 +235,7 @@ __device__ __forceinline__ uint32_t group8_sad(const T *sp, int sstride, const T
       }
     }
   }
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-  return acc;
+  return row8_sum(acc);
 }
 
 // The same SAD with the candidate addressed as a UNIFORM base (SGPR pair: the wavefront's block) + a 32-bit byte offset per lane: the
@@ -204,10 +272,7 @@ __device__ __forceinline__ uint32_t group8_sad_u(const char *base, uint32_t site
       }
     }
   }
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-  return acc;
+  return row8_sum(acc);
 }
 
 // The same SAD with the reference block taken from an LDS window (byte offset `off` of the block's top-left pixel,
@@ -241,16 +306,7 @@ __device__ __forceinline__ uint32_t group8_sad_lds(const uint32_t *win, unsigned
       }
     }
   }
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0xB1, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x4E, 0xf, 0xf, false);
-  acc += __builtin_amdgcn_update_dpp(0u, acc, 0x141, 0xf, 0xf, false);
-  return acc;
-}
-
-__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor((long long)v, m, 64);
-  return v;
+  return row8_sum(acc);
 }
 
 // Variance (SUBPEL = false) or bilinear sub-pixel variance of a W x H block by all 64 lanes.  a = "ref" operand
@@ -292,25 +348,7 @@ __device__ __forceinline__ uint32_t wave_variance(const T *ap, int astride, int 
   }
   sum = wave_sum64(sum);
   sse = wave_sum64(sse);
-  // variance.c:141-148 / :383-420
-  int32_t s;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)(((uint64_t)sse + 8) >> 4);
-    s = (int32_t)((sum + 2) >> 2);
-  } else if (bit_depth == 12) {
-    q = (uint32_t)(((uint64_t)sse + 128) >> 8);
-    s = (int32_t)((sum + 8) >> 4);
-  } else {
-    q = (uint32_t)sse;
-    s = (int32_t)sum;
-  }
-  *sse_out = q;
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)s * s) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  return finish_var<W, H>(sum, (uint64_t)sse, bit_depth, sse_out);
 }
 
 // ---- 16 lanes per candidate: up to four independent candidates of one block are evaluated side by side -------------
@@ -321,13 +359,6 @@ __device__ __forceinline__ uint32_t wave_variance(const T *ap, int astride, int 
 template <typename T> __device__ __forceinline__ int px_of(const uint32_t *v, int i) {
   if constexpr (sizeof(T) == 2) return (int)((v[i >> 1] >> (16 * (i & 1))) & 0xffffu);
   else return (int)((v[i >> 2] >> (8 * (i & 3))) & 0xffu);
-}
-__device__ __forceinline__ uint32_t row16_sum_u32(uint32_t v) {
-  v += __builtin_amdgcn_update_dpp(0u, v, 0xB1, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x4E, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x141, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0u, v, 0x140, 0xf, 0xf, false);
-  return v;
 }
 // The minimum of a key over the wavefront when the 8 lanes of each group already hold their group's key: the row's other group (row_ror:8),
 // then row_bcast15 into rows 1 and 3 and row_bcast31 into rows 2 and 3, the result read from lane 63 -- three v_min_u32 with the DPP operand
@@ -340,18 +371,6 @@ __device__ __forceinline__ uint32_t groups8_min_u32(uint32_t key) {
                : "+v"(key));
   return (uint32_t)__builtin_amdgcn_readlane((int)key, 63);
 }
-__device__ __forceinline__ uint64_t row16_sum_u64(uint64_t v) {
-#define AOMHIP_STEP64(CTRL)                                                                      \
-  {                                                                                              \
-    const uint32_t lo = __builtin_amdgcn_update_dpp(0u, (uint32_t)v, CTRL, 0xf, 0xf, false);     \
-    const uint32_t hi = __builtin_amdgcn_update_dpp(0u, (uint32_t)(v >> 32), CTRL, 0xf, 0xf, false); \
-    v += ((uint64_t)hi << 32) | lo;                                                              \
-  }
-  AOMHIP_STEP64(0xB1) AOMHIP_STEP64(0x4E) AOMHIP_STEP64(0x141) AOMHIP_STEP64(0x140)
-#undef AOMHIP_STEP64
-  return v;
-}
-
 // The other reference's predictor of a compound search (ms_buffers.second_pred / mask / inv_mask): `second` W x H pixels, `mask` W x H blend
 // weights 0..64 or null.  blend(): aom_comp_avg_pred (variance.c:306-319) / aom_comp_mask_pred (:773-791, AOM_BLEND_A64) on one pixel, `f` the
 // (filtered) pixel of the searched reference.
@@ -533,32 +552,11 @@ __device__ __forceinline__ uint32_t group16_variance(const T *ap, int astride, i
       sse += uq;
     }
   }
-  int64_t tsum = (int64_t)(int32_t)row16_sum_u32((uint32_t)sum);
-  uint64_t tsse = row16_sum_u64(sse);
+  int64_t tsum = (int64_t)row16_sum(sum);
+  uint64_t tsse = row16_sum(sse);
   if (nparts > 1) parts_sum(tsum, tsse, nparts);
-  int32_t sfin;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)((tsse + 8) >> 4);
-    sfin = (int32_t)((tsum + 2) >> 2);
-  } else if (bit_depth == 12) {
-    q = (uint32_t)((tsse + 128) >> 8);
-    sfin = (int32_t)((tsum + 8) >> 4);
-  } else {
-    q = (uint32_t)tsse;
-    sfin = (int32_t)tsum;
-  }
-  *sse_out = q;
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)sfin * sfin) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  return finish_var<W, H>(tsum, tsse, bit_depth, sse_out);
 }
-
-#define AOMHIP_FOR_BLOCK_SIZES(X)                                                                                \
-  X(4, 4) X(4, 8) X(8, 4) X(8, 8) X(8, 16) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32) X(32, 64) X(64, 32) \
-  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
 
 inline int check_common(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *ref, int frame, int bw, int bh,
                         const void *blocks, int n, int cost_type) {

@@ -260,30 +260,8 @@ __device__ __forceinline__ uint32_t group8_variance_lds(const uint32_t *win, uns
   }
   int32_t sum = (int32_t)ssum - (int32_t)rsum;
   uint32_t sse = ss + rr - 2u * sr;
-  sum += __builtin_amdgcn_update_dpp(0, sum, 0xB1, 0xf, 0xf, false);
-  sum += __builtin_amdgcn_update_dpp(0, sum, 0x4E, 0xf, 0xf, false);
-  sum += __builtin_amdgcn_update_dpp(0, sum, 0x141, 0xf, 0xf, false);
-  sse += __builtin_amdgcn_update_dpp(0u, sse, 0xB1, 0xf, 0xf, false);
-  sse += __builtin_amdgcn_update_dpp(0u, sse, 0x4E, 0xf, 0xf, false);
-  sse += __builtin_amdgcn_update_dpp(0u, sse, 0x141, 0xf, 0xf, false);
-  // variance.c:141-148 / :383-420 (the same finish as group16_variance)
-  int32_t sfin;
   uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)(((uint64_t)sse + 8) >> 4);
-    sfin = (sum + 2) >> 2;
-  } else if (bit_depth == 12) {
-    q = (uint32_t)(((uint64_t)sse + 128) >> 8);
-    sfin = (sum + 8) >> 4;
-  } else {
-    q = sse;
-    sfin = sum;
-  }
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)sfin * sfin) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  return finish_var<W, H>(row8_sum(sum), row8_sum(sse), bit_depth, &q);
 }
 
 }  // namespace aomhip

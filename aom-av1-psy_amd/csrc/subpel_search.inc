@@ -257,29 +257,12 @@ __device__ __forceinline__ uint32_t group16_upsampled_variance(const T *ap, int 
   };
   if (narrow) strips(std::true_type{});
   else strips(std::false_type{});
-  int64_t tsum = (int64_t)(int32_t)row16_sum_u32((uint32_t)sum);
-  uint64_t tsse = row16_sum_u64(sse);
+  int64_t tsum = (int64_t)row16_sum(sum);
+  uint64_t tsse = row16_sum(sse);
   if (nparts > 1) parts_sum(tsum, tsse, nparts);
-  int32_t sfin;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)((tsse + 8) >> 4);
-    sfin = (int32_t)((tsum + 2) >> 2);
-  } else if (bit_depth == 12) {
-    q = (uint32_t)((tsse + 128) >> 8);
-    sfin = (int32_t)((tsum + 8) >> 4);
-  } else {
-    q = (uint32_t)tsse;
-    sfin = (int32_t)tsum;
-  }
-  *sse_out = q;
   UPS_ADD(3, UPS_T() - ups_t0);
   UPS_ADD(4, 1);
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)sfin * sfin) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  return finish_var<W, H>(tsum, tsse, bit_depth, sse_out);
 }
 
 // MV_COST_ENTROPY inputs of the sub-pel search (mv_err_cost, mcomp.c:271-295): joint[4] and the two component tables
@@ -534,26 +517,9 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
       }
     }
   }
-  const int64_t tsum = (int64_t)(int32_t)row16_sum_u32((uint32_t)sum);
-  const uint64_t tsse = row16_sum_u64(sse);
-  int32_t sfin;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)((tsse + 8) >> 4);
-    sfin = (int32_t)((tsum + 2) >> 2);
-  } else if (bit_depth == 12) {
-    q = (uint32_t)((tsse + 128) >> 8);
-    sfin = (int32_t)((tsum + 8) >> 4);
-  } else {
-    q = (uint32_t)tsse;
-    sfin = (int32_t)tsum;
-  }
-  *sse_out = q;
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)sfin * sfin) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  const int64_t tsum = (int64_t)row16_sum(sum);
+  const uint64_t tsse = row16_sum(sse);
+  return finish_var<W, H>(tsum, tsse, bit_depth, sse_out);
 }
 
 // ONE candidate by the whole wavefront (16-bit planes, blocks of 32 row units = 16x16 / 32x8 / 8x32): a round of the tree that holds a single
@@ -608,27 +574,10 @@ __device__ __forceinline__ uint32_t wave_variance_foot(const uint32_t *foot, int
     }
   }
   // two DPP rows hold the block: each row's sums (128 pixels x 2^24 < 2^32), then the two rows on the scalar unit
-  const uint32_t rs = row16_sum_u32((uint32_t)us), rq = row16_sum_u32(uq);
+  const uint32_t rs = row16_sum((uint32_t)us), rq = row16_sum(uq);
   const int64_t tsum = (int64_t)(int32_t)__builtin_amdgcn_readlane((int)rs, 0) + (int64_t)(int32_t)__builtin_amdgcn_readlane((int)rs, 16);
   const uint64_t tsse = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rq, 0) + (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)rq, 16);
-  int32_t sfin;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)((tsse + 8) >> 4);
-    sfin = (int32_t)((tsum + 2) >> 2);
-  } else if (bit_depth == 12) {
-    q = (uint32_t)((tsse + 128) >> 8);
-    sfin = (int32_t)((tsum + 8) >> 4);
-  } else {
-    q = (uint32_t)tsse;
-    sfin = (int32_t)tsum;
-  }
-  *sse_out = q;
-  constexpr int LOG2N = __builtin_ctz(W * H);
-  const int64_t sq = ((int64_t)sfin * sfin) >> LOG2N;
-  if (bit_depth == 8) return q - (uint32_t)sq;
-  const int64_t v = (int64_t)q - sq;
-  return v >= 0 ? (uint32_t)v : 0;
+  return finish_var<W, H>(tsum, tsse, bit_depth, sse_out);
 }
 
 // GENERAL = false is the lean instantiation behind aomhip_subpel_bilinear_batch (pruned_more, no cost list, L1 / no MV
@@ -675,7 +624,7 @@ __global__ __launch_bounds__(kSearchThreads, (subpel_waves<W, H, GENERAL>())) vo
   if (b.row_min > b.row_max) return;   // an EMPTY window marks a block the caller wants skipped (fullpel_search.inc): outputs stay as they are
   const T *sp = src.origin + (int64_t)frame * src.frame_stride + (int64_t)b.by * src.stride + b.bx;
   const T *rbase = ref.origin + (int64_t)frame * ref.frame_stride + (int64_t)b.by * ref.stride + b.bx;
-  const CostCtx cc{ cost_type, b.ref_row, b.ref_col };
+  const MvCost<GENERAL> mc(cost_type, b.ref_row, b.ref_col, 0, ct.error_per_bit, ct.mvjcost, ct.mvcost0, ct.mvcost1);   // (the lean instantiation: L1 / no MV cost)
   // a compound search: every error measures the blend of the (filtered) reference with the other reference's predictor -- vfp->svaf / msvf
   // (estimated_pref_error, mcomp.c:2311-2337) or the comp_avg / comp_mask up-sampled prediction (upsampled_pref_error, :2339-2428)
   // (by value, `second` null when the search is not a compound one: as a pointer to a local chosen at run time the three fields lived in
@@ -688,15 +637,6 @@ __global__ __launch_bounds__(kSearchThreads, (subpel_waves<W, H, GENERAL>())) vo
       comp.invert = ct.invert_mask;
     }
   }
-  auto var_cost = [&](int mrow, int mcol) -> int {  // mv_err_cost_ (mcomp.c:271-308)
-    if (GENERAL && cost_type == kCostEntropy) {
-      const int dr = mrow - b.ref_row, dc = mcol - b.ref_col;
-      const int64_t bits = ct.mvjcost[(dc != 0) | ((dr != 0) << 1)] + ct.mvcost0[dr] + ct.mvcost1[dc];
-      return (int)((bits * ct.error_per_bit + (1 << 13)) >> 14);
-    }
-    return cc.var_cost(mrow, mcol);
-  };
-
   const int grp = lane >> 4, j = lane & 15;
   // the search's reference footprint in LDS + the source block in registers (bilinear error only; blocks up to 32 x 32)
   using F = Foot<T, W, H>;
@@ -774,7 +714,7 @@ __global__ __launch_bounds__(kSearchThreads, (subpel_waves<W, H, GENERAL>())) vo
     v = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);   // (v_readlane: __shfl is a ds_bpermute round trip through the LDS pipe)
     sse1 = (uint32_t)__builtin_amdgcn_readlane((int)q, 0);
     distortion = (int)v;
-    besterr = v + (uint32_t)var_cost(b.start_row, b.start_col);
+    besterr = v + (uint32_t)mc.var(b.start_row, b.start_col);
   }
   // check_better_fast (mcomp.c:2433-2461) for up to four candidates whose POSITIONS do not depend on each other:
   // group g evaluates candidate g (one aom_sub_pixel_varianceWxH each), then every lane replays the reference's
@@ -822,7 +762,7 @@ __global__ __launch_bounds__(kSearchThreads, (subpel_waves<W, H, GENERAL>())) vo
         const bool in_k = mcol[k] >= b.col_min && mcol[k] <= b.col_max && mrow[k] >= b.row_min && mrow[k] <= b.row_max;
         if (in_k) {
           const int thismse = (int)vk;
-          cost[k] = (uint32_t)var_cost(mrow[k], mcol[k]) + (uint32_t)thismse;
+          cost[k] = (uint32_t)mc.var(mrow[k], mcol[k]) + (uint32_t)thismse;
           if (cost[k] < besterr) {
             besterr = cost[k];
             best_row = mrow[k];

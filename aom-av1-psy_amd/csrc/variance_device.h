@@ -1,10 +1,11 @@
 // Shared device pieces of the variance-family kernels (variance.hip, compound.hip): unaligned wide loads, the
-// row-unit geometry of a W x H block over TPC lanes, group reductions and the reference's final formulas
-// (aom_dsp/variance.c:141-148 VAR, :383-420 HIGHBD_VAR).
+// row-unit geometry of a W x H block over TPC lanes and group reductions; the reference's final formulas are finish<> of
+// variance_finish.h.
 #pragma once
 #include <type_traits>
 
 #include "common.h"
+#include "variance_finish.h"
 
 namespace aomhip {
 
@@ -58,36 +59,7 @@ template <typename T, int N> __device__ __forceinline__ void load_elems(const T 
   }
 }
 
-// variance.c:141-148 VAR / :383-420 HIGHBD_VAR final formulas
-template <int BD_CLASS /*0: 8-bit planes*/, int LOG2N>
-__device__ __forceinline__ void finish(int64_t sum64, uint64_t sse64, int bit_depth, uint32_t *var, uint32_t *sse) {
-  int32_t s;
-  uint32_t q;
-  if (bit_depth == 10) {
-    q = (uint32_t)((sse64 + 8) >> 4);
-    s = (int32_t)((sum64 + 2) >> 2);  // arithmetic shift of a possibly negative sum (aom_ports/mem.h:45)
-  } else if (bit_depth == 12) {
-    q = (uint32_t)((sse64 + 128) >> 8);
-    s = (int32_t)((sum64 + 8) >> 4);
-  } else {
-    q = (uint32_t)sse64;
-    s = (int32_t)sum64;
-  }
-  *sse = q;
-  const int64_t sq = ((int64_t)s * s) >> LOG2N;  // sum^2 >= 0: shift == division by W*H
-  if (bit_depth == 8) {
-    *var = q - (uint32_t)sq;
-  } else {
-    const int64_t v = (int64_t)q - sq;
-    *var = v >= 0 ? (uint32_t)v : 0;
-  }
-}
-
 constexpr int ilog2v(int n) { return n <= 1 ? 0 : 1 + ilog2v(n >> 1); }
 constexpr int kVarThreads = 256;
-
-#define AOMHIP_FOR_BLOCK_SIZES(X)                                                                                \
-  X(4, 4) X(4, 8) X(8, 4) X(8, 8) X(8, 16) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32) X(32, 64) X(64, 32) \
-  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
 
 }  // namespace aomhip

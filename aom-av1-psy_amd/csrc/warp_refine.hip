@@ -31,17 +31,6 @@ struct WrCand {         // per (block, neighbour) of a round
   aomhip_warp_model model;
 };
 
-__device__ __forceinline__ int wr_mv_cost(int mrow, int mcol, int ref_row, int ref_col, int cost_type, int error_per_bit, const int32_t *mvjcost,
-                                          const int32_t *mvcost0, const int32_t *mvcost1) {   // mv_err_cost_ (mcomp.c:271-308)
-  const int dr = mrow - ref_row, dc = mcol - ref_col;
-  if (cost_type == kCostEntropy) {
-    const int64_t bits = (int64_t)mvjcost[(dc != 0) | ((dr != 0) << 1)] + mvcost0[dr] + mvcost1[dc];
-    return (int)((bits * error_per_bit + (1 << 13)) >> 14);
-  }
-  const int lambda = cost_type == kCostL1Low ? 2 : cost_type == kCostL1Hd ? 1 : 0;   // (L1_MIDRES: 0, mcomp.c:300)
-  return (lambda * (iabsm(dr) + iabsm(dc))) >> 3;
-}
-
 __device__ __forceinline__ aomhip_warp_block wr_record(const aomhip_warp_model &m, int bx, int by, int w, int h) {
   aomhip_warp_block r;
 #pragma unroll
@@ -72,7 +61,7 @@ __global__ void wr_center_kernel(const aomhip_warp_refine_block *__restrict__ bl
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const aomhip_warp_refine_block b = blocks[i];
-  st[i].bestmse = (int32_t)(var[i] + (uint32_t)wr_mv_cost(b.mv_row, b.mv_col, b.ref_row, b.ref_col, cost_type, error_per_bit, mvjcost, mvcost0, mvcost1));
+  st[i].bestmse = (int32_t)(var[i] + (uint32_t)MvCost<>(cost_type, b.ref_row, b.ref_col, 0, error_per_bit, mvjcost, mvcost0, mvcost1).var(b.mv_row, b.mv_col));   // mv_err_cost_
 }
 
 // one lane per (block, neighbour j): the candidate's model, or an empty rectangle
@@ -118,12 +107,13 @@ __global__ void wr_pick_kernel(const aomhip_warp_refine_block *__restrict__ bloc
   WrState s = st[i];
   if (!s.active) return;
   const aomhip_warp_refine_block b = blocks[i];
+  const MvCost<> mc(cost_type, b.ref_row, b.ref_col, 0, error_per_bit, mvjcost, mvcost0, mvcost1);
   int best = -1;
   for (int j = 0; j < 4; ++j) {
     const WrCand c = cand[4 * i + j];
     // mbmi->num_proj_ref follows every in-range candidate's selection, used or not (it only matters for a block with one sample, where it never changes)
     if (!c.valid) continue;
-    const uint32_t mse = var[(int64_t)j * n + i] + (uint32_t)wr_mv_cost(c.mv_row, c.mv_col, b.ref_row, b.ref_col, cost_type, error_per_bit, mvjcost, mvcost0, mvcost1);
+    const uint32_t mse = var[(int64_t)j * n + i] + (uint32_t)mc.var(c.mv_row, c.mv_col);
     if (mse < (uint32_t)s.bestmse) {
       best = j;
       s.bestmse = (int32_t)mse;
