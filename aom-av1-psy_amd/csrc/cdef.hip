@@ -83,11 +83,37 @@ template <int D> __device__ __forceinline__ int dir_cost(const int (&x)[64]) {
   return cost;
 }
 
-// Cdef_Directions (AV1 spec 7.15.3; cdef_block.c:25-48) as LDS offsets dy * kTW + dx for taps k = 0, 1
-__device__ constexpr int kDirOff[8][2] = {
-  { -1 * kTW + 1, -2 * kTW + 2 }, { 0 * kTW + 1, -1 * kTW + 2 }, { 0 * kTW + 1, 0 * kTW + 2 }, { 0 * kTW + 1, 1 * kTW + 2 },
-  { 1 * kTW + 1, 2 * kTW + 2 },   { 1 * kTW + 0, 2 * kTW + 1 },  { 1 * kTW + 0, 2 * kTW + 0 }, { 1 * kTW + 0, 2 * kTW - 1 }
-};
+// best direction of a block and its variance from the eight direction costs (cdef_block.c:103-126)
+struct DirVar { int dir, var; };
+__device__ __forceinline__ DirVar best_direction(const int (&cost)[8]) {
+  int best = 0, best_cost = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (cost[k] > best_cost) {
+      best_cost = cost[k];
+      best = k;
+    }
+  int orth = cost[0];
+#pragma unroll
+  for (int k = 1; k < 8; ++k) orth = (((best + 4) & 7) == k) ? cost[k] : orth;
+  return { best, (best_cost - orth) >> 10 };
+}
+
+// Cdef_Directions (AV1 spec 7.15.3; cdef_block.c:25-48): { dy, dx } of taps k = 0, 1 of each direction
+__device__ constexpr int8_t kDirDyDx[8][2][2] = { { { -1, 1 }, { -2, 2 } }, { { 0, 1 }, { -1, 2 } }, { { 0, 1 }, { 0, 2 } },
+                                                  { { 0, 1 }, { 1, 2 } },   { { 1, 1 }, { 2, 2 } },  { { 1, 0 }, { 2, 1 } },
+                                                  { { 1, 0 }, { 2, 0 } },   { { 1, 0 }, { 2, -1 } } };
+// ... as an element offset at row pitch `pitch`
+__host__ __device__ constexpr int dir_off(int d, int k, int pitch) { return kDirDyDx[d][k][0] * pitch + kDirDyDx[d][k][1]; }
+// ... and as a table at the luma tile's pitch (one load per offset where the direction is not a compile-time constant)
+struct DirOffTable { int v[8][2]; };
+__host__ __device__ constexpr DirOffTable dir_off_table(int pitch) {
+  DirOffTable t{};
+  for (int d = 0; d < 8; ++d)
+    for (int k = 0; k < 2; ++k) t.v[d][k] = dir_off(d, k, pitch);
+  return t;
+}
+__device__ constexpr DirOffTable kDirOff = dir_off_table(kTW);
 
 // Packed int16 pairs (two pixels per VGPR; clang lowers the element-wise operators to v_pk_* on gfx950)
 typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -106,13 +132,71 @@ __device__ __forceinline__ s16x2 constrain_pk(s16x2 diff, s16x2 thr, s16x2 shift
   return pmax(pmin(diff, lim), -lim);
 }
 
-// constrain() with the shift (damping - msb(threshold), floored at 0) hoisted out; threshold 0 gives 0 by itself
-__device__ __forceinline__ int constrain_s(int diff, int threshold, int shift) {
-  const int a = diff < 0 ? -diff : diff;
-  int m = threshold - (a >> shift);
-  m = m < 0 ? 0 : m;
-  m = m > a ? a : m;
-  return diff < 0 ? -m : m;
+// What cdef_filter_block_internal (cdef_block.c:139-201) is called with, for the pixel pairs of one block
+struct CdefTaps {
+  int po0, po1, s1o0, s1o1, s2o0, s2o1;               // tile offsets of the primary taps and of the two secondary pairs, k = 0, 1
+  s16x2 pt0, pt1, pri_thr, pri_sh, sec_thr, sec_sh;   // cdef_pri_taps; threshold and shift of constrain_pk per strength
+  bool clip;                                          // both strengths on: the result is clipped to the taps' range
+};
+// strengths: `t` is the primary strength as the filter sees it (after adjust_strength for luma), dmp the plane's damping (luma: damping + coeff_shift,
+// chroma: one less, cdef_block.c:333)
+__device__ __forceinline__ void cdef_set_strengths(CdefTaps &k, int t, int sec_strength, int dmp, int coeff_shift) {
+  const int sec_shift = sec_strength ? max(0, dmp - msb_u((unsigned)sec_strength)) : 0;
+  const int pri_shift = t ? max(0, dmp - msb_u((unsigned)t)) : 0;
+  k.clip = (t != 0) && (sec_strength != 0);
+  k.pt0 = splat2(((t >> coeff_shift) & 1) ? 3 : 4), k.pt1 = splat2(((t >> coeff_shift) & 1) ? 3 : 2);
+  k.pri_thr = splat2(t), k.pri_sh = splat2(pri_shift), k.sec_thr = splat2(sec_strength), k.sec_sh = splat2(sec_shift);
+}
+// direction: off(d, k) is the tile offset of tap k of direction d
+template <typename OFF> __device__ __forceinline__ void cdef_set_direction(CdefTaps &k, int dir, OFF off) {
+  k.po0 = off(dir, 0), k.po1 = off(dir, 1);
+  k.s1o0 = off((dir + 2) & 7, 0), k.s1o1 = off((dir + 2) & 7, 1);
+  k.s2o0 = off((dir + 6) & 7, 0), k.s2o1 = off((dir + 6) & 7, 1);
+}
+
+// The filter on two vertically adjacent pixels x; ld2(off) loads the pair at tile offset `off` from them.  mask_large: taps may be CDEF_VERY_LARGE
+// (outside the frame), which must not enter the maximum: & 0x3fff turns it into 0 and leaves pixels alone.  Only a filter block on the frame's
+// edge has such taps staged; the others (91 % of a 4K luma frame) skip the twelve ANDs.
+template <typename LD> __device__ __forceinline__ s16x2 cdef_filter_pair(LD ld2, s16x2 x, const CdefTaps &t, bool mask_large) {
+  const s16x2 p0 = ld2(t.po0), p1 = ld2(-t.po0), p2 = ld2(t.po1), p3 = ld2(-t.po1);
+  const s16x2 a0 = ld2(t.s1o0), a1 = ld2(-t.s1o0), a2 = ld2(t.s2o0), a3 = ld2(-t.s2o0);
+  const s16x2 c0 = ld2(t.s1o1), c1 = ld2(-t.s1o1), c2 = ld2(t.s2o1), c3 = ld2(-t.s2o1);
+  s16x2 sum = t.pt0 * (constrain_pk(p0 - x, t.pri_thr, t.pri_sh) + constrain_pk(p1 - x, t.pri_thr, t.pri_sh)) +
+              t.pt1 * (constrain_pk(p2 - x, t.pri_thr, t.pri_sh) + constrain_pk(p3 - x, t.pri_thr, t.pri_sh));
+  const s16x2 sa = constrain_pk(a0 - x, t.sec_thr, t.sec_sh) + constrain_pk(a1 - x, t.sec_thr, t.sec_sh) +
+                   constrain_pk(a2 - x, t.sec_thr, t.sec_sh) + constrain_pk(a3 - x, t.sec_thr, t.sec_sh);
+  const s16x2 sc = constrain_pk(c0 - x, t.sec_thr, t.sec_sh) + constrain_pk(c1 - x, t.sec_thr, t.sec_sh) +
+                   constrain_pk(c2 - x, t.sec_thr, t.sec_sh) + constrain_pk(c3 - x, t.sec_thr, t.sec_sh);
+  sum += sa + sa + sc;
+  // y = x + ((8 + sum - (sum < 0)) >> 4): (sum < 0) is -(sum >> 15)
+  s16x2 y = x + ((splat2(8) + sum + (sum >> splat2(15))) >> splat2(4));
+  if (t.clip) {
+    s16x2 mx;
+    if (mask_large) {
+      const s16x2 k = splat2(0x3fff);
+      mx = pmax(pmax(pmax(x, p0 & k), pmax(p1 & k, p2 & k)), pmax(pmax(p3 & k, a0 & k), pmax(a1 & k, a2 & k)));
+      mx = pmax(pmax(pmax(mx, a3 & k), pmax(c0 & k, c1 & k)), pmax(c2 & k, c3 & k));
+    } else {
+      mx = pmax(pmax(pmax(x, p0), pmax(p1, p2)), pmax(pmax(p3, a0), pmax(a1, a2)));
+      mx = pmax(pmax(pmax(mx, a3), pmax(c0, c1)), pmax(c2, c3));
+    }
+    s16x2 mn = pmin(pmin(pmin(x, p0), pmin(p1, p2)), pmin(pmin(p3, a0), pmin(a1, a2)));
+    mn = pmin(pmin(pmin(mn, a3), pmin(c0, c1)), pmin(c2, c3));
+    y = pmin(pmax(y, mn), mx);
+  }
+  return y;
+}
+
+// SEARCH epilogue of one strength: the workgroup's four wavefronts' squared errors summed into *out.  (The first barrier: the previous
+// strength's swave has been consumed.)
+__device__ __forceinline__ void cdef_store_error(uint32_t err, unsigned long long *swave, int wave, int lane, uint64_t *out) {
+  unsigned long long tot = err;
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) tot += __shfl_xor(tot, m, 64);
+  __syncthreads();
+  if (lane == 0) swave[wave] = tot;
+  __syncthreads();
+  if (threadIdx.x == 0) *out = swave[0] + swave[1] + swave[2] + swave[3];
 }
 
 // SEARCH = false: the filtering pass (dst = CDEF(src) with each filter block's strengths).
@@ -217,18 +301,8 @@ __global__ __launch_bounds__(256) void cdef_luma_kernel(const PIX *__restrict__ 
       int cost[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) cost[k] = scost[k][tid];
-      int best = 0, best_cost = 0;
-#pragma unroll
-      for (int k = 0; k < 8; ++k)
-        if (cost[k] > best_cost) {
-          best_cost = cost[k];
-          best = k;
-        }
-      int orth = cost[0];
-#pragma unroll
-      for (int k = 1; k < 8; ++k) orth = (((best + 4) & 7) == k) ? cost[k] : orth;
-      var = (best_cost - orth) >> 10;
-      d = best;
+      const DirVar best = best_direction(cost);
+      d = best.dir, var = best.var;
     }
     sdir[tid] = (int8_t)d;
     svar[tid] = var;
@@ -271,8 +345,6 @@ __global__ __launch_bounds__(256) void cdef_luma_kernel(const PIX *__restrict__ 
   [[maybe_unused]] uint32_t err = 0;
   const int pri_strength = level << coeff_shift, sec_strength = sec << coeff_shift;
   const int dmp = damping + coeff_shift;
-  const int sec_shift = sec_strength ? max(0, dmp - msb_u((unsigned)sec_strength)) : 0;
-  const s16x2 sec_thr = splat2(sec_strength), sec_sh = splat2(sec_shift);
 #pragma unroll 1
   for (int half = 0; half < 2; ++half) {
     const int by = wave * 2 + half, bx = lane >> 3, blk = by * 8 + bx;
@@ -284,51 +356,16 @@ __global__ __launch_bounds__(256) void cdef_luma_kernel(const PIX *__restrict__ 
       const int i = (var >> 6) ? min(msb_u((unsigned)(var >> 6)), 12) : 0;
       t = var ? (pri_strength * (4 + i) + 8) >> 4 : 0;
     }
-    const int pri_shift = t ? max(0, dmp - msb_u((unsigned)t)) : 0;
-    const int dir = pri_strength ? (d < 0 ? 0 : d) : 0;
-    const bool clip = (t != 0) && (sec_strength != 0);
-    const s16x2 pt0 = splat2(((t >> coeff_shift) & 1) ? 3 : 4), pt1 = splat2(((t >> coeff_shift) & 1) ? 3 : 2);  // cdef_pri_taps
-    const s16x2 pri_thr = splat2(t), pri_sh = splat2(pri_shift);
-    const int po0 = kDirOff[dir][0], po1 = kDirOff[dir][1];
-    const int s1o0 = kDirOff[(dir + 2) & 7][0], s1o1 = kDirOff[(dir + 2) & 7][1];
-    const int s2o0 = kDirOff[(dir + 6) & 7][0], s2o1 = kDirOff[(dir + 6) & 7][1];
+    CdefTaps taps;
+    cdef_set_strengths(taps, t, sec_strength, dmp, coeff_shift);
+    cdef_set_direction(taps, pri_strength ? (d < 0 ? 0 : d) : 0, [](int dir, int k) { return kDirOff.v[dir][k]; });
 #pragma unroll 2
     for (int rr = 0; rr < 8; rr += 2) {
       const int ly = by * 8 + rr;
       const int pos = (ly + 2) * kTW + lane + 4;
       auto ld2 = [&](int off) { return pack2(tile[pos + off], tile[pos + kTW + off]); };  // rows ly and ly + 1
       const s16x2 x = ld2(0);
-      s16x2 y = x;
-      if (d >= 0) {
-        const s16x2 p0 = ld2(po0), p1 = ld2(-po0), p2 = ld2(po1), p3 = ld2(-po1);
-        const s16x2 a0 = ld2(s1o0), a1 = ld2(-s1o0), a2 = ld2(s2o0), a3 = ld2(-s2o0);
-        const s16x2 c0 = ld2(s1o1), c1 = ld2(-s1o1), c2 = ld2(s2o1), c3 = ld2(-s2o1);
-        s16x2 sum = pt0 * (constrain_pk(p0 - x, pri_thr, pri_sh) + constrain_pk(p1 - x, pri_thr, pri_sh)) +
-                    pt1 * (constrain_pk(p2 - x, pri_thr, pri_sh) + constrain_pk(p3 - x, pri_thr, pri_sh));
-        const s16x2 sa = constrain_pk(a0 - x, sec_thr, sec_sh) + constrain_pk(a1 - x, sec_thr, sec_sh) +
-                         constrain_pk(a2 - x, sec_thr, sec_sh) + constrain_pk(a3 - x, sec_thr, sec_sh);
-        const s16x2 sc = constrain_pk(c0 - x, sec_thr, sec_sh) + constrain_pk(c1 - x, sec_thr, sec_sh) +
-                         constrain_pk(c2 - x, sec_thr, sec_sh) + constrain_pk(c3 - x, sec_thr, sec_sh);
-        sum += sa + sa + sc;
-        // y = x + ((8 + sum - (sum < 0)) >> 4): (sum < 0) is -(sum >> 15)
-        y = x + ((splat2(8) + sum + (sum >> splat2(15))) >> splat2(4));
-        if (clip) {
-          // CDEF_VERY_LARGE (0x4000) must not enter the maximum: & 0x3fff turns it into 0 and leaves pixels alone.  Only a filter block
-          // on the frame's edge has such taps staged; the others (91 % of a 4K frame) skip the twelve ANDs.
-          s16x2 mx;
-          if (fb_on_edge) {
-            const s16x2 k = splat2(0x3fff);
-            mx = pmax(pmax(pmax(x, p0 & k), pmax(p1 & k, p2 & k)), pmax(pmax(p3 & k, a0 & k), pmax(a1 & k, a2 & k)));
-            mx = pmax(pmax(pmax(mx, a3 & k), pmax(c0 & k, c1 & k)), pmax(c2 & k, c3 & k));
-          } else {
-            mx = pmax(pmax(pmax(x, p0), pmax(p1, p2)), pmax(pmax(p3, a0), pmax(a1, a2)));
-            mx = pmax(pmax(pmax(mx, a3), pmax(c0, c1)), pmax(c2, c3));
-          }
-          s16x2 mn = pmin(pmin(pmin(x, p0), pmin(p1, p2)), pmin(pmin(p3, a0), pmin(a1, a2)));
-          mn = pmin(pmin(pmin(mn, a3), pmin(c0, c1)), pmin(c2, c3));
-          y = pmin(pmax(y, mn), mx);
-        }
-      }
+      const s16x2 y = d >= 0 ? cdef_filter_pair(ld2, x, taps, fb_on_edge) : x;
       if constexpr (SEARCH) {
         if (d >= 0) {  // only the blocks of the filter list count (compute_cdef_dist*, pickcdef.c:237-315)
           const int e0 = og[half * 8 + rr] - (int)y.x, e1 = og[half * 8 + rr + 1] - (int)y.y;
@@ -341,16 +378,7 @@ __global__ __launch_bounds__(256) void cdef_luma_kernel(const PIX *__restrict__ 
       }
     }
   }
-  if constexpr (SEARCH) {
-    unsigned long long tot = err;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) tot += __shfl_xor(tot, m, 64);
-    __syncthreads();  // the previous strength's swave has been consumed
-    if (lane == 0) swave[wave] = tot;
-    __syncthreads();
-    if (tid == 0)
-      sa_.sse[(int64_t)gi * gridDim.y * fb_stride + fby * fb_stride + fbx] = swave[0] + swave[1] + swave[2] + swave[3];
-  }
+  if constexpr (SEARCH) cdef_store_error(err, swave, wave, lane, &sa_.sse[(int64_t)gi * gridDim.y * fb_stride + fby * fb_stride + fbx]);
   }  // strengths
 }
 
@@ -358,10 +386,6 @@ __global__ __launch_bounds__(256) void cdef_luma_kernel(const PIX *__restrict__ 
 // (8 >> XDEC) x (8 >> YDEC) chroma block; the direction comes from luma (converted for 4:2:2 / 4:4:0, :362-371),
 // the primary strength is not variance-adjusted and the damping is one less (:333).  Same structure as the luma
 // kernel without the direction search: one workgroup per filter block, footprint in LDS, 4 lanes per block.
-__device__ constexpr int8_t kDirDyDx[8][2][2] = { { { -1, 1 }, { -2, 2 } }, { { 0, 1 }, { -1, 2 } }, { { 0, 1 }, { 0, 2 } },
-                                                  { { 0, 1 }, { 1, 2 } },   { { 1, 1 }, { 2, 2 } },  { { 1, 0 }, { 2, 1 } },
-                                                  { { 1, 0 }, { 2, 0 } },   { { 1, 0 }, { 2, -1 } } };
-
 // SEARCH as in cdef_luma_kernel: fb_pri = the (pri, sec) list, only the per-strength squared-error sums are written.
 template <typename PIX, int XDEC, int YDEC, bool SEARCH>
 __global__ __launch_bounds__(256) void cdef_chroma_kernel(const PIX *__restrict__ src, PIX *__restrict__ dst, int stride,
@@ -413,14 +437,8 @@ __global__ __launch_bounds__(256) void cdef_chroma_kernel(const PIX *__restrict_
   }
   [[maybe_unused]] uint32_t err = 0;
   const int pri_strength = level << coeff_shift, sec_strength = sec << coeff_shift;
-  const int dmp = damping + coeff_shift - 1;
-  const int t = pri_strength;
-  const int pri_shift = t ? max(0, dmp - msb_u((unsigned)t)) : 0;
-  const int sec_shift = sec_strength ? max(0, dmp - msb_u((unsigned)sec_strength)) : 0;
-  const bool clip = (t != 0) && (sec_strength != 0);
-  const s16x2 pri_thr = splat2(t), pri_sh = splat2(pri_shift), sec_thr = splat2(sec_strength), sec_sh = splat2(sec_shift);
-  const s16x2 pt0 = splat2(((t >> coeff_shift) & 1) ? 3 : 4), pt1 = splat2(((t >> coeff_shift) & 1) ? 3 : 2);
-  auto off = [&](int d, int k) { return kDirDyDx[d][k][0] * TW + kDirDyDx[d][k][1]; };
+  CdefTaps taps;
+  cdef_set_strengths(taps, pri_strength, sec_strength, damping + coeff_shift - 1, coeff_shift);
 #pragma unroll 1
   for (int step = 0; step < kRowsPerWave / (2 * kSub); ++step) {
     const int ly = wave * kRowsPerWave + (step * kSub + rsub) * 2;   // rows ly, ly + 1 (same chroma block: BH is 4 or 8)
@@ -436,35 +454,11 @@ __global__ __launch_bounds__(256) void cdef_chroma_kernel(const PIX *__restrict_
       for (int k = 0; k < 8; ++k) c = dir == k ? (XDEC ? conv422[k] : conv440[k]) : c;
       dir = c;
     }
-    dir = pri_strength ? dir : 0;
-    const int po0 = off(dir, 0), po1 = off(dir, 1);
-    const int s1o0 = off((dir + 2) & 7, 0), s1o1 = off((dir + 2) & 7, 1);
-    const int s2o0 = off((dir + 6) & 7, 0), s2o1 = off((dir + 6) & 7, 1);
+    cdef_set_direction(taps, pri_strength ? dir : 0, [](int d, int k) { return dir_off(d, k, TW); });
     const int pos = (ly + 2) * TW + col + 4;
     auto ld2 = [&](int o) { return pack2(tile[pos + o], tile[pos + TW + o]); };
     const s16x2 x = ld2(0);
-    s16x2 y = x;
-    if (filt) {
-      const s16x2 p0 = ld2(po0), p1 = ld2(-po0), p2 = ld2(po1), p3 = ld2(-po1);
-      const s16x2 a0 = ld2(s1o0), a1 = ld2(-s1o0), a2 = ld2(s2o0), a3 = ld2(-s2o0);
-      const s16x2 c0 = ld2(s1o1), c1 = ld2(-s1o1), c2 = ld2(s2o1), c3 = ld2(-s2o1);
-      s16x2 sum = pt0 * (constrain_pk(p0 - x, pri_thr, pri_sh) + constrain_pk(p1 - x, pri_thr, pri_sh)) +
-                  pt1 * (constrain_pk(p2 - x, pri_thr, pri_sh) + constrain_pk(p3 - x, pri_thr, pri_sh));
-      const s16x2 sa = constrain_pk(a0 - x, sec_thr, sec_sh) + constrain_pk(a1 - x, sec_thr, sec_sh) +
-                       constrain_pk(a2 - x, sec_thr, sec_sh) + constrain_pk(a3 - x, sec_thr, sec_sh);
-      const s16x2 sc = constrain_pk(c0 - x, sec_thr, sec_sh) + constrain_pk(c1 - x, sec_thr, sec_sh) +
-                       constrain_pk(c2 - x, sec_thr, sec_sh) + constrain_pk(c3 - x, sec_thr, sec_sh);
-      sum += sa + sa + sc;
-      y = x + ((splat2(8) + sum + (sum >> splat2(15))) >> splat2(4));
-      if (clip) {
-        const s16x2 k = splat2(0x3fff);
-        s16x2 mx = pmax(pmax(pmax(x, p0 & k), pmax(p1 & k, p2 & k)), pmax(pmax(p3 & k, a0 & k), pmax(a1 & k, a2 & k)));
-        mx = pmax(pmax(pmax(mx, a3 & k), pmax(c0 & k, c1 & k)), pmax(c2 & k, c3 & k));
-        s16x2 mn = pmin(pmin(pmin(x, p0), pmin(p1, p2)), pmin(pmin(p3, a0), pmin(a1, a2)));
-        mn = pmin(pmin(pmin(mn, a3), pmin(c0, c1)), pmin(c2, c3));
-        y = pmin(pmax(y, mn), mx);
-      }
-    }
+    const s16x2 y = filt ? cdef_filter_pair(ld2, x, taps, true) : x;   // (every chroma block masks: the kernel is not the measured path)
     if constexpr (SEARCH) {
       if (!skip[bidx]) {  // only the units of the filter list count (compute_cdef_dist*, pickcdef.c:237-315)
         const PIX *op = static_cast<const PIX *>(sa_.orig) + (int64_t)gy * sa_.orig_stride + gx;
@@ -477,16 +471,7 @@ __global__ __launch_bounds__(256) void cdef_chroma_kernel(const PIX *__restrict_
       o[stride] = (PIX)(uint16_t)y.y;
     }
   }
-  if constexpr (SEARCH) {
-    unsigned long long tot = err;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) tot += __shfl_xor(tot, m, 64);
-    __syncthreads();
-    if (lane == 0) swave[wave] = tot;
-    __syncthreads();
-    if (tid == 0)
-      sa_.sse[(int64_t)gi * gridDim.y * fb_stride + fby * fb_stride + fbx] = swave[0] + swave[1] + swave[2] + swave[3];
-  }
+  if constexpr (SEARCH) cdef_store_error(err, swave, wave, lane, &sa_.sse[(int64_t)gi * gridDim.y * fb_stride + fby * fb_stride + fbx]);
   }  // strengths
 }
 
@@ -506,15 +491,9 @@ __global__ __launch_bounds__(64) void cdef_find_dir_kernel(const uint16_t *__res
   int cost[8];
   cost[0] = dir_cost<0>(x); cost[1] = dir_cost<1>(x); cost[2] = dir_cost<2>(x); cost[3] = dir_cost<3>(x);
   cost[4] = dir_cost<4>(x); cost[5] = dir_cost<5>(x); cost[6] = dir_cost<6>(x); cost[7] = dir_cost<7>(x);
-  int best = 0, best_cost = 0;
-#pragma unroll
-  for (int d = 0; d < 8; ++d)
-    if (cost[d] > best_cost) { best_cost = cost[d]; best = d; }
-  int orth = 0;
-#pragma unroll
-  for (int d = 0; d < 8; ++d) orth = d == ((best + 4) & 7) ? cost[d] : orth;
-  out[2 * b] = best;
-  out[2 * b + 1] = (best_cost - orth) >> 10;
+  const DirVar best = best_direction(cost);
+  out[2 * b] = best.dir;
+  out[2 * b + 1] = best.var;
 }
 
 // cdef_filter_block_internal (cdef_block.c:139-281) = cdef_filter_{8,16}_{0..3}_c: `in` is the staged (bh + 4) x (bw + 4)
@@ -535,7 +514,7 @@ __global__ __launch_bounds__(64) void cdef_filter_block_kernel(const uint16_t *_
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     if (enable_primary) {
-      const int o = kDirDyDx[dir][k][0] * s + kDirDyDx[dir][k][1];
+      const int o = dir_off(dir, k, s);
       const int p0 = c[o], p1 = c[-o];
       sum += pri_taps[ps][k] * (constrain_d(p0 - x, pri_strength, pri_damping) + constrain_d(p1 - x, pri_strength, pri_damping));
       if (clip) {
@@ -545,8 +524,7 @@ __global__ __launch_bounds__(64) void cdef_filter_block_kernel(const uint16_t *_
       }
     }
     if (enable_secondary) {
-      const int o1 = kDirDyDx[(dir + 2) & 7][k][0] * s + kDirDyDx[(dir + 2) & 7][k][1];
-      const int o2 = kDirDyDx[(dir + 6) & 7][k][0] * s + kDirDyDx[(dir + 6) & 7][k][1];
+      const int o1 = dir_off((dir + 2) & 7, k, s), o2 = dir_off((dir + 6) & 7, k, s);
       const int q[4] = { c[o1], c[-o1], c[o2], c[-o2] };
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -563,18 +541,40 @@ __global__ __launch_bounds__(64) void cdef_filter_block_kernel(const uint16_t *_
   out[t] = (uint16_t)y;
 }
 
-template <typename PIX, bool SEARCH>
-static void launch_chroma(hipStream_t st, dim3 grid, int xdec, int ydec, const void *s, void *d, int stride, int w, int h,
-                          const uint8_t *dir, const uint8_t *pri, const uint8_t *sec, int fbs, const uint8_t *skip,
-                          int damping, int cs, const CdefSearchArgs &sa = CdefSearchArgs{}) {
-#define AOMHIP_CDEF_C(X, Y)                                                                                          \
-  hipLaunchKernelGGL((cdef_chroma_kernel<PIX, X, Y, SEARCH>), grid, dim3(256), 0, st, static_cast<const PIX *>(s),   \
-                     static_cast<PIX *>(d), stride, w, h, dir, pri, sec, fbs, skip, damping, cs, sa)
-  if (xdec == 1 && ydec == 1) AOMHIP_CDEF_C(1, 1);
-  else if (xdec == 0 && ydec == 0) AOMHIP_CDEF_C(0, 0);
-  else if (xdec == 1 && ydec == 0) AOMHIP_CDEF_C(1, 0);
-  else AOMHIP_CDEF_C(0, 1);
+static int fb_count(int size, int dec) { return (size + (64 >> dec) - 1) / (64 >> dec); }   // filter blocks along one dimension of a plane
+
+// What the four plane entry points check alike: frame `af` of ring `a` against frame `bf` of ring `b` (the destination, or the source frame of
+// the search), whole (8 >> xdec) x (8 >> ydec) blocks, the damping and the pitch of the per-filter-block arrays.
+static bool cdef_planes_ok(const aomhip_planes *a, int af, const aomhip_planes *b, int bf, int xdec, int ydec, int damping, int fb_stride) {
+  return valid_frame(a, af) && valid_frame(b, bf) && same_visible(a, b) && xdec >= 0 && xdec <= 1 && ydec >= 0 && ydec <= 1 &&
+         a->width % (8 >> xdec) == 0 && a->height % (8 >> ydec) == 0 && damping >= 3 && damping <= 6 && fb_stride >= fb_count(a->width, xdec);
+}
+
+// The launch of a plane.  luma_dir: null for the luma plane.  SEARCH = false: src -> `other`, filtered with fb_pri / fb_sec.  SEARCH = true: the
+// n_strengths pairs at fb_pri applied to src and compared with `other`, the sums to `sse`.
+template <bool SEARCH>
+static void launch_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *other, int other_frame, int xdec, int ydec,
+                         const uint8_t *luma_dir, const uint8_t *fb_pri, const uint8_t *fb_sec, int fb_stride, const uint8_t *skip, int damping,
+                         uint8_t *dir_out, int32_t *var_out, int n_strengths, uint64_t *sse) {
+  const dim3 grid(fb_count(src->width, xdec), fb_count(src->height, ydec));
+  with_pixel(src->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    const T *s = pixels<T>(src, src_frame);
+    T *o = pixels<T>(other, other_frame), *d = SEARCH ? nullptr : o;
+    const CdefSearchArgs sa = SEARCH ? CdefSearchArgs{ o, other->stride, n_strengths, sse } : CdefSearchArgs{};
+    const int w = src->width, h = src->height, cs = src->bit_depth - 8;
+#define AOMHIP_CDEF_C(X, Y)                                                                                                                \
+  hipLaunchKernelGGL((cdef_chroma_kernel<T, X, Y, SEARCH>), grid, dim3(256), 0, ctx->stream, s, d, src->stride, w, h, luma_dir, fb_pri, \
+                     fb_sec, fb_stride, skip, damping, cs, sa)
+    if (!luma_dir)
+      hipLaunchKernelGGL((cdef_luma_kernel<T, SEARCH>), grid, dim3(256), 0, ctx->stream, s, d, src->stride, w, h, fb_pri, fb_sec, fb_stride, skip,
+                         damping, cs, dir_out, var_out, sa);
+    else if (xdec == 1 && ydec == 1) AOMHIP_CDEF_C(1, 1);
+    else if (xdec == 0 && ydec == 0) AOMHIP_CDEF_C(0, 0);
+    else if (xdec == 1 && ydec == 0) AOMHIP_CDEF_C(1, 0);
+    else AOMHIP_CDEF_C(0, 1);
 #undef AOMHIP_CDEF_C
+  });
 }
 
 extern "C" {
@@ -582,29 +582,13 @@ extern "C" {
 int aomhip_cdef_luma_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dst,
                            int dst_frame, const uint8_t *d_fb_pri, const uint8_t *d_fb_sec, int fb_stride,
                            const uint8_t *d_skip8x8, int damping, uint8_t *d_dir_out, int32_t *d_var_out) {
-  if (!ctx || !src || !dst || !src->base || !dst->base || !d_fb_pri || !d_fb_sec || !d_skip8x8 || src_frame < 0 ||
-      src_frame >= src->n_frames || dst_frame < 0 || dst_frame >= dst->n_frames || src->width != dst->width ||
-      src->height != dst->height || src->stride != dst->stride || src->bit_depth != dst->bit_depth ||
-      (src->width & 7) || (src->height & 7) || damping < 3 || damping > 6 || fb_stride < (src->width + 63) / 64 ||
-      (src->base == dst->base && src_frame == dst_frame)) {
+  if (!ctx || !d_fb_pri || !d_fb_sec || !d_skip8x8 || !cdef_planes_ok(src, src_frame, dst, dst_frame, 0, 0, damping, fb_stride) ||
+      src->stride != dst->stride || same_frame(src, src_frame, dst, dst_frame)) {
     set_error("aomhip_cdef_luma_plane: invalid argument (dimensions must be multiples of 8, out of place)");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = src->bit_depth == 8 ? 1 : 2;
-  const char *s = static_cast<const char *>(src->base) +
-                  ((size_t)src_frame * src->frame_stride + (size_t)src->border * src->stride + src->border) * esz;
-  char *d = static_cast<char *>(dst->base) +
-            ((size_t)dst_frame * dst->frame_stride + (size_t)dst->border * dst->stride + dst->border) * esz;
-  const dim3 grid((src->width + 63) / 64, (src->height + 63) / 64);
-  if (esz == 1)
-    hipLaunchKernelGGL((cdef_luma_kernel<uint8_t, false>), grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t *>(s),
-                       reinterpret_cast<uint8_t *>(d), src->stride, src->width, src->height, d_fb_pri, d_fb_sec,
-                       fb_stride, d_skip8x8, damping, 0, d_dir_out, d_var_out, CdefSearchArgs{});
-  else
-    hipLaunchKernelGGL((cdef_luma_kernel<uint16_t, false>), grid, dim3(256), 0, ctx->stream,
-                       reinterpret_cast<const uint16_t *>(s), reinterpret_cast<uint16_t *>(d), src->stride, src->width,
-                       src->height, d_fb_pri, d_fb_sec, fb_stride, d_skip8x8, damping, src->bit_depth - 8, d_dir_out,
-                       d_var_out, CdefSearchArgs{});
+  launch_plane<false>(ctx, src, src_frame, dst, dst_frame, 0, 0, nullptr, d_fb_pri, d_fb_sec, fb_stride, d_skip8x8, damping, d_dir_out, d_var_out, 0,
+                      nullptr);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -612,28 +596,13 @@ int aomhip_cdef_luma_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_fr
 int aomhip_cdef_search_sse_luma(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *source,
                                 int source_frame, const uint8_t *d_strengths, int n_strengths, const uint8_t *d_skip8x8, int damping,
                                 int fb_stride, uint64_t *d_sse, uint8_t *d_dir_out, int32_t *d_var_out) {
-  if (!ctx || !recon || !source || !recon->base || !source->base || !d_strengths || n_strengths <= 0 || n_strengths > 64 || !d_skip8x8 ||
-      !d_sse || recon_frame < 0 || recon_frame >= recon->n_frames || source_frame < 0 || source_frame >= source->n_frames ||
-      recon->width != source->width || recon->height != source->height || recon->bit_depth != source->bit_depth || (recon->width & 7) ||
-      (recon->height & 7) || damping < 3 || damping > 6 || fb_stride < (recon->width + 63) / 64) {
+  if (!ctx || !d_strengths || n_strengths <= 0 || n_strengths > 64 || !d_skip8x8 || !d_sse ||
+      !cdef_planes_ok(recon, recon_frame, source, source_frame, 0, 0, damping, fb_stride)) {
     set_error("aomhip_cdef_search_sse_luma: invalid argument");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = recon->bit_depth == 8 ? 1 : 2;
-  const char *s = static_cast<const char *>(recon->base) +
-                  ((size_t)recon_frame * recon->frame_stride + (size_t)recon->border * recon->stride + recon->border) * esz;
-  const char *o = static_cast<const char *>(source->base) +
-                  ((size_t)source_frame * source->frame_stride + (size_t)source->border * source->stride + source->border) * esz;
-  const dim3 grid((recon->width + 63) / 64, (recon->height + 63) / 64);
-  const CdefSearchArgs sa{ o, source->stride, n_strengths, d_sse };
-  if (esz == 1)
-    hipLaunchKernelGGL((cdef_luma_kernel<uint8_t, true>), grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t *>(s),
-                       static_cast<uint8_t *>(nullptr), recon->stride, recon->width, recon->height, d_strengths, d_strengths, fb_stride,
-                       d_skip8x8, damping, 0, d_dir_out, d_var_out, sa);
-  else
-    hipLaunchKernelGGL((cdef_luma_kernel<uint16_t, true>), grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint16_t *>(s),
-                       static_cast<uint16_t *>(nullptr), recon->stride, recon->width, recon->height, d_strengths, d_strengths, fb_stride,
-                       d_skip8x8, damping, recon->bit_depth - 8, d_dir_out, d_var_out, sa);
+  launch_plane<true>(ctx, recon, recon_frame, source, source_frame, 0, 0, nullptr, d_strengths, d_strengths, fb_stride, d_skip8x8, damping, d_dir_out,
+                     d_var_out, n_strengths, d_sse);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -641,27 +610,14 @@ int aomhip_cdef_search_sse_luma(aomhip_ctx *ctx, const aomhip_planes *recon, int
 int aomhip_cdef_chroma_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dst,
                              int dst_frame, int xdec, int ydec, const uint8_t *d_luma_dir, const uint8_t *d_fb_uv_pri,
                              const uint8_t *d_fb_uv_sec, int fb_stride, const uint8_t *d_skip8x8, int damping) {
-  if (!ctx || !src || !dst || !src->base || !dst->base || !d_luma_dir || !d_fb_uv_pri || !d_fb_uv_sec || !d_skip8x8 ||
-      src_frame < 0 || src_frame >= src->n_frames || dst_frame < 0 || dst_frame >= dst->n_frames ||
-      src->width != dst->width || src->height != dst->height || src->stride != dst->stride ||
-      src->bit_depth != dst->bit_depth || xdec < 0 || xdec > 1 || ydec < 0 || ydec > 1 ||
-      (src->width % (8 >> xdec)) || (src->height % (8 >> ydec)) || damping < 3 || damping > 6 ||
-      fb_stride < (src->width + (64 >> xdec) - 1) / (64 >> xdec) || (src->base == dst->base && src_frame == dst_frame)) {
+  if (!ctx || !d_luma_dir || !d_fb_uv_pri || !d_fb_uv_sec || !d_skip8x8 ||
+      !cdef_planes_ok(src, src_frame, dst, dst_frame, xdec, ydec, damping, fb_stride) || src->stride != dst->stride ||
+      same_frame(src, src_frame, dst, dst_frame)) {
     set_error("aomhip_cdef_chroma_plane: invalid argument (chroma size must be whole blocks, out of place)");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = src->bit_depth == 8 ? 1 : 2;
-  const char *s = static_cast<const char *>(src->base) +
-                  ((size_t)src_frame * src->frame_stride + (size_t)src->border * src->stride + src->border) * esz;
-  char *d = static_cast<char *>(dst->base) +
-            ((size_t)dst_frame * dst->frame_stride + (size_t)dst->border * dst->stride + dst->border) * esz;
-  const dim3 grid((src->width + (64 >> xdec) - 1) / (64 >> xdec), (src->height + (64 >> ydec) - 1) / (64 >> ydec));
-  if (esz == 1)
-    launch_chroma<uint8_t, false>(ctx->stream, grid, xdec, ydec, s, d, src->stride, src->width, src->height, d_luma_dir,
-                           d_fb_uv_pri, d_fb_uv_sec, fb_stride, d_skip8x8, damping, 0);
-  else
-    launch_chroma<uint16_t, false>(ctx->stream, grid, xdec, ydec, s, d, src->stride, src->width, src->height, d_luma_dir,
-                            d_fb_uv_pri, d_fb_uv_sec, fb_stride, d_skip8x8, damping, src->bit_depth - 8);
+  launch_plane<false>(ctx, src, src_frame, dst, dst_frame, xdec, ydec, d_luma_dir, d_fb_uv_pri, d_fb_uv_sec, fb_stride, d_skip8x8, damping, nullptr,
+                      nullptr, 0, nullptr);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -669,27 +625,13 @@ int aomhip_cdef_chroma_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_
 int aomhip_cdef_search_sse_chroma(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *source,
                                   int source_frame, int xdec, int ydec, const uint8_t *d_luma_dir, const uint8_t *d_strengths,
                                   int n_strengths, const uint8_t *d_skip8x8, int damping, int fb_stride, uint64_t *d_sse) {
-  if (!ctx || !recon || !source || !recon->base || !source->base || !d_luma_dir || !d_strengths || n_strengths <= 0 || n_strengths > 64 ||
-      !d_skip8x8 || !d_sse || recon_frame < 0 || recon_frame >= recon->n_frames || source_frame < 0 || source_frame >= source->n_frames ||
-      recon->width != source->width || recon->height != source->height || recon->bit_depth != source->bit_depth || xdec < 0 || xdec > 1 ||
-      ydec < 0 || ydec > 1 || (recon->width % (8 >> xdec)) || (recon->height % (8 >> ydec)) || damping < 3 || damping > 6 ||
-      fb_stride < (recon->width + (64 >> xdec) - 1) / (64 >> xdec)) {
+  if (!ctx || !d_luma_dir || !d_strengths || n_strengths <= 0 || n_strengths > 64 || !d_skip8x8 || !d_sse ||
+      !cdef_planes_ok(recon, recon_frame, source, source_frame, xdec, ydec, damping, fb_stride)) {
     set_error("aomhip_cdef_search_sse_chroma: invalid argument");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = recon->bit_depth == 8 ? 1 : 2;
-  const char *s = static_cast<const char *>(recon->base) +
-                  ((size_t)recon_frame * recon->frame_stride + (size_t)recon->border * recon->stride + recon->border) * esz;
-  const char *o = static_cast<const char *>(source->base) +
-                  ((size_t)source_frame * source->frame_stride + (size_t)source->border * source->stride + source->border) * esz;
-  const dim3 grid((recon->width + (64 >> xdec) - 1) / (64 >> xdec), (recon->height + (64 >> ydec) - 1) / (64 >> ydec));
-  const CdefSearchArgs sa{ o, source->stride, n_strengths, d_sse };
-  if (esz == 1)
-    launch_chroma<uint8_t, true>(ctx->stream, grid, xdec, ydec, s, nullptr, recon->stride, recon->width, recon->height, d_luma_dir, d_strengths,
-                                 d_strengths, fb_stride, d_skip8x8, damping, 0, sa);
-  else
-    launch_chroma<uint16_t, true>(ctx->stream, grid, xdec, ydec, s, nullptr, recon->stride, recon->width, recon->height, d_luma_dir,
-                                  d_strengths, d_strengths, fb_stride, d_skip8x8, damping, recon->bit_depth - 8, sa);
+  launch_plane<true>(ctx, recon, recon_frame, source, source_frame, xdec, ydec, d_luma_dir, d_strengths, d_strengths, fb_stride, d_skip8x8, damping,
+                     nullptr, nullptr, n_strengths, d_sse);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

@@ -124,6 +124,14 @@ auto with_pixel(int bit_depth, F &&f) {
   return f(uint16_t{});
 }
 
+// argument checks of the plane-taking entry points: a valid frame of a valid ring; two rings of the same visible geometry and depth; the same frame
+// of the same ring
+inline bool valid_frame(const aomhip_planes *p, int frame) { return p && p->base && frame >= 0 && frame < p->n_frames; }
+inline bool same_visible(const aomhip_planes *a, const aomhip_planes *b) {
+  return a->width == b->width && a->height == b->height && a->bit_depth == b->bit_depth;
+}
+inline bool same_frame(const aomhip_planes *a, int a_frame, const aomhip_planes *b, int b_frame) { return a->base == b->base && a_frame == b_frame; }
+
 // one frame of a ring as a ring of one (the batched searches pair src / ref by frame index)
 inline aomhip_planes one_frame(const aomhip_planes &p, int f) {
   aomhip_planes v = p;

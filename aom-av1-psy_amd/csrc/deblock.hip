@@ -27,8 +27,28 @@ struct __attribute__((packed, aligned(1))) DU128 { uint32_t v[4]; };
 struct __attribute__((packed, aligned(4))) DU128A4 { uint32_t v[4]; };   // 16 bytes at a 4-byte boundary
 struct __attribute__((packed, aligned(1))) DU64 { uint32_t v[2]; };
 
-__device__ __forceinline__ int iabsd(int v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ int clampd(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// Pixels an edge of filter length `len` reads (reach) and writes (zone) on each side of it.  Macros, not functions: a function, however declared, is
+// inlined in another shape than the expression written in place and costs deblock_horz4_kernel two registers -- 81 instead of 79, five wavefronts
+// per SIMD instead of six on the 4K path.
+#define AOMHIP_LPF_REACH(len) ((len) == 14 ? 7 : ((len) == 8 ? 4 : ((len) == 6 ? 3 : 2)))
+#define AOMHIP_LPF_ZONE(len) ((len) == 14 ? 6 : ((len) == 8 ? 3 : 2))
+
+// The taps x[0 .. 13] = pixels 1 .. 14 of a 16-pixel window that starts 8 pixels before q0: 8-bit pixels in one 16-byte piece, 16-bit pixels in two
+// (W: anything with the dwords in .v[4])
+template <typename W> __device__ __forceinline__ void lpf_unpack(int (&x)[14], const W &w) {
+#pragma unroll
+  for (int i = 0; i < 14; ++i) x[i] = (int)((w.v[(i + 1) / 4] >> (8 * ((i + 1) % 4))) & 0xFF);
+}
+template <typename W> __device__ __forceinline__ void lpf_unpack(int (&x)[14], const W &lo, const W &hi) {
+#pragma unroll
+  for (int i = 0; i < 14; ++i) {
+    const int px = i + 1;  // index within the 16-pixel window
+    const uint32_t d = px < 8 ? lo.v[px / 2] : hi.v[(px - 8) / 2];
+    x[i] = (d >> (16 * (px % 2))) & 0xFFFF;
+  }
+}
 
 // x[7 + i] holds tap i (i = -7 .. 6: p6 .. p0, q0 .. q6); filters in place.  lim8 / blim8 / thr8: the 8-bit thresholds
 // the reference's functions take as *limit / *blimit / *thresh (scaled by bd - 8 inside, loopfilter.c:521-522,568,596).
@@ -140,7 +160,7 @@ __global__ __launch_bounds__(64) void lpf_edge_kernel(PIX *patch, int horizontal
                                                       int blim0, int thr0, int lim1, int blim1, int thr1, int bd) {
   const int i = threadIdx.x;
   if (i >= count) return;
-  const int reach = len == 14 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
+  const int reach = AOMHIP_LPF_REACH(len);
   int x[14];
 #pragma unroll
   for (int k = 0; k < 14; ++k) {
@@ -176,17 +196,9 @@ __global__ __launch_bounds__(kDbThreads) void deblock_vert_kernel(PIX *origin, i
   PIX *s = origin + (int64_t)y * stride + 4 * ux;  // q0
   int x[14];
   if constexpr (sizeof(PIX) == 1) {
-    const DU128 w = *reinterpret_cast<const DU128 *>(s - 8);  // pixels x-8 .. x+7
-#pragma unroll
-    for (int i = 0; i < 14; ++i) x[i] = (w.v[(i + 1) / 4] >> (8 * ((i + 1) % 4))) & 0xFF;
+    lpf_unpack(x, *reinterpret_cast<const DU128 *>(s - 8));  // pixels x-8 .. x+7
   } else {
-    const DU128 w0 = *reinterpret_cast<const DU128 *>(s - 8), w1 = *reinterpret_cast<const DU128 *>(s);
-#pragma unroll
-    for (int i = 0; i < 14; ++i) {
-      const int px = i + 1;  // index within the 16-pixel window
-      const uint32_t d = px < 8 ? w0.v[px / 2] : w1.v[(px - 8) / 2];
-      x[i] = (d >> (16 * (px % 2))) & 0xFFFF;
-    }
+    lpf_unpack(x, *reinterpret_cast<const DU128 *>(s - 8), *reinterpret_cast<const DU128 *>(s));
   }
   lpf_window(x, len, level, sharpness, bd);
   // write back only this edge's own zone
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(kDbThreads) void deblock_horz_kernel(PIX *origin, i
   const int len = e[2], level = e[3];
   if (len == 0 || level == 0) return;
   PIX *s = origin + (int64_t)(4 * uy) * stride + xcol;  // q0
-  const int reach = len == 14 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
+  const int reach = AOMHIP_LPF_REACH(len);
   int x[14];
 #pragma unroll
   for (int i = 0; i < 14; ++i) {
@@ -223,7 +235,7 @@ __global__ __launch_bounds__(kDbThreads) void deblock_horz_kernel(PIX *origin, i
     x[i] = (k >= -reach && k < reach) ? (int)s[(int64_t)k * stride] : 0;
   }
   lpf_window(x, len, level, sharpness, bd);
-  const int wr = len == 14 ? 6 : (len == 8 ? 3 : 2);
+  const int wr = AOMHIP_LPF_ZONE(len);
 #pragma unroll
   for (int i = 1; i <= 12; ++i) {
     const int k = i - 7;
@@ -254,10 +266,8 @@ __global__ __launch_bounds__(kDbThreads) void deblock_vert4_kernel(PIX *origin, 
     for (int r = 0; r < 4; ++r) w[r] = *reinterpret_cast<const DU128A4 *>(s + (int64_t)r * stride - 8);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const uint32_t (&wv)[4] = w[r].v;
       int x[14];
-#pragma unroll
-      for (int i = 0; i < 14; ++i) x[i] = (int)((wv[(i + 1) / 4] >> (8 * ((i + 1) % 4))) & 0xFF);
+      lpf_unpack(x, w[r]);
       lpf_window(x, len, level, sharpness, bd);
       // this edge's own zone only, cut at its natural alignments: q0 is a dword boundary, x - 6 and x - 2 are halfword boundaries
       uint8_t *sr = s + (int64_t)r * stride;
@@ -288,12 +298,7 @@ __global__ __launch_bounds__(kDbThreads) void deblock_vert4_kernel(PIX *origin, 
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     int x[14];
-#pragma unroll
-    for (int i = 0; i < 14; ++i) {
-      const int px = i + 1;  // index within the 16-pixel window
-      const uint32_t d = px < 8 ? w0[r].v[px / 2] : w1[r].v[(px - 8) / 2];
-      x[i] = (d >> (16 * (px % 2))) & 0xFFFF;
-    }
+    lpf_unpack(x, w0[r], w1[r]);
     lpf_window(x, len, level, sharpness, bd);
     // this edge's own zone only (the neighbours' zones are theirs to write), as few stores as its 4-byte alignment allows: the edge sits at
     // a multiple of 4 pixels, so x - 6 and x - 2 are dword boundaries (the one-line kernel issues a 2-byte store per pixel)
@@ -323,8 +328,8 @@ __global__ __launch_bounds__(kDbThreads) void deblock_horz4_kernel(PIX *origin, 
   const int len = e[2], level = e[3];
   if (len == 0 || level == 0) return;
   PIX *s = origin + (int64_t)(4 * uy) * stride + 4 * ux;  // q0 of the unit's first column
-  const int reach = len == 14 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
-  const int wr = len == 14 ? 6 : (len == 8 ? 3 : 2);
+  const int reach = AOMHIP_LPF_REACH(len);
+  const int wr = AOMHIP_LPF_ZONE(len);
   int out[4][14];
   if constexpr (sizeof(PIX) == 1) {   // 8-bit planes: the unit's four columns of a row are one dword
     uint32_t rows[14];
@@ -438,15 +443,10 @@ __global__ __launch_bounds__(kDbThreads) void deblock_fused_kernel(const PIX *__
     const int len = rec & 0xFF, level = (rec >> 8) & 0xFF;
     if (len == 0 || level == 0) continue;
     uint16_t *row = &tile[r * kFPitch + 4 * e];   // pixels x - 8 .. x + 7 of the edge at x = x0 + 4 e (q0 = row[8])
-    uint32_t w[8];
-    {
-      const uint2 a = *reinterpret_cast<const uint2 *>(row), b = *reinterpret_cast<const uint2 *>(row + 4), c = *reinterpret_cast<const uint2 *>(row + 8),
-                  d = *reinterpret_cast<const uint2 *>(row + 12);
-      w[0] = a.x; w[1] = a.y; w[2] = b.x; w[3] = b.y; w[4] = c.x; w[5] = c.y; w[6] = d.x; w[7] = d.y;
-    }
+    const uint2 a = *reinterpret_cast<const uint2 *>(row), b = *reinterpret_cast<const uint2 *>(row + 4), c = *reinterpret_cast<const uint2 *>(row + 8),
+                d = *reinterpret_cast<const uint2 *>(row + 12);
     int x[14];
-#pragma unroll
-    for (int i = 0; i < 14; ++i) x[i] = (w[(i + 1) / 2] >> (16 * ((i + 1) % 2))) & 0xFFFF;
+    lpf_unpack(x, DU128{ { a.x, a.y, b.x, b.y } }, DU128{ { c.x, c.y, d.x, d.y } });
     lpf_window(x, len, level, sharpness, bd);
     // the edge's own zone: p5 .. q5 (len 14), p2 .. q2 (8), p1 .. q1 (4, 6) -- pairs of pixels at dword-aligned positions
     if (len == 14) {
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kDbThreads) void deblock_fused_kernel(const PIX *__
     const uint32_t rec = sp[(k + kFHalo / 4) * kFUCols + (c2 >> 1)];
     const int len = (rec >> 16) & 0xFF, level = rec >> 24;
     if (len == 0 || level == 0) continue;
-    const int reach = len == 14 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
+    const int reach = AOMHIP_LPF_REACH(len);
     uint32_t *col = reinterpret_cast<uint32_t *>(&tile[(kFHalo + 4 * k) * kFPitch + kFHalo + 2 * c2]);   // q0 of both columns
     constexpr int kPd = kFPitch / 2;
     int xa[14], xb[14];
@@ -483,7 +483,7 @@ __global__ __launch_bounds__(kDbThreads) void deblock_fused_kernel(const PIX *__
     }
     lpf_window(xa, len, level, sharpness, bd);
     if (xg + 1 < width) lpf_window(xb, len, level, sharpness, bd);
-    const int wr = len == 14 ? 6 : (len == 8 ? 3 : 2);
+    const int wr = AOMHIP_LPF_ZONE(len);
 #pragma unroll
     for (int i = 1; i <= 12; ++i) {
       const int t = i - 7;
@@ -582,12 +582,20 @@ __global__ __launch_bounds__(256) void plane_sse_kernel(const T *__restrict__ a,
 
 using namespace aomhip;
 
+// aom_get_sse_plane of frame a_frame of ring `a` against frame b_frame of ring `b` (the same visible size and depth) added to *out
+static void launch_plane_sse(aomhip_ctx *ctx, const aomhip_planes *a, int a_frame, const aomhip_planes *b, int b_frame, uint64_t *out) {
+  with_pixel(a->bit_depth, [&](auto px) {
+    using T = decltype(px);
+    hipLaunchKernelGGL(plane_sse_kernel<T>, dim3((a->height + 3) / 4), dim3(256), 0, ctx->stream, pixels<T>(a, a_frame), a->stride,
+                       pixels<T>(b, b_frame), b->stride, a->width, a->height, reinterpret_cast<unsigned long long *>(out));   // a wavefront per row
+  });
+}
+
 extern "C" {
 
 int aomhip_deblock_plane(aomhip_ctx *ctx, const aomhip_planes *p, int frame, const uint8_t *d_edge_params,
                          int units_stride, int sharpness, int passes) {
-  if (!ctx || !p || !p->base || !d_edge_params || frame < 0 || frame >= p->n_frames || sharpness < 0 ||
-      sharpness > 7 || units_stride < (p->width + 3) / 4) {
+  if (!ctx || !valid_frame(p, frame) || !d_edge_params || sharpness < 0 || sharpness > 7 || units_stride < (p->width + 3) / 4) {
     set_error("aomhip_deblock_plane: invalid argument");
     return AOMHIP_ERR_INVALID;
   }
@@ -595,73 +603,40 @@ int aomhip_deblock_plane(aomhip_ctx *ctx, const aomhip_planes *p, int frame, con
     set_error("aomhip_deblock_plane: the vertical pass needs a border of >= 4 pixels (plane has %d)", p->border);
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = p->bit_depth == 8 ? 1 : 2;
-  char *origin = static_cast<char *>(p->base) +
-                 ((size_t)frame * p->frame_stride + (size_t)p->border * p->stride + p->border) * esz;
   const int ucols = (p->width + 3) / 4, urows = (p->height + 3) / 4;
   const int rows_per_wg = kDbThreads / 64;
-  const dim3 gv((ucols + 63) / 64, (p->height + rows_per_wg - 1) / rows_per_wg);
-  const dim3 gh((p->width + 63) / 64, (urows + rows_per_wg - 1) / rows_per_wg);
-  // planes whose rows keep 4-pixel groups naturally aligned (8 bytes at 16 bits, 4 at 8): four lines of an edge per lane (AOMHIP_DEBLOCK_LINES=1: the one-line kernels, A/B)
   const char *one = getenv("AOMHIP_DEBLOCK_LINES");
-  const bool four = (p->width & 3) == 0 && (p->height & 3) == 0 && (p->stride & 3) == 0 && (p->border & 3) == 0 && p->border >= 8 &&
-                    (reinterpret_cast<uintptr_t>(origin) & (4 * esz - 1)) == 0 && !(one && atoi(one) == 1);
-  if (four) {
+  return with_pixel(p->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+    T *origin = pixels<T>(p, frame);
+    // planes whose rows keep 4-pixel groups naturally aligned (8 bytes at 16 bits, 4 at 8): four lines of an edge per lane (AOMHIP_DEBLOCK_LINES=1: the one-line kernels, A/B)
+    const bool four = (p->width & 3) == 0 && (p->height & 3) == 0 && (p->stride & 3) == 0 && (p->border & 3) == 0 && p->border >= 8 &&
+                      (reinterpret_cast<uintptr_t>(origin) & (4 * sizeof(T) - 1)) == 0 && !(one && atoi(one) == 1);
+    // [four lines][pass]: vertical edges, then horizontal
+    void (*const kernel[2][2])(T *, int, int, int, const uint8_t *, int, int, int) = { { deblock_vert_kernel<T>, deblock_horz_kernel<T> },
+                                                                                      { deblock_vert4_kernel<T>, deblock_horz4_kernel<T> } };
     const dim3 g4((ucols + 63) / 64, (urows + rows_per_wg - 1) / rows_per_wg);
-    if (passes & 1) {
-      if (esz == 1)
-        hipLaunchKernelGGL(deblock_vert4_kernel<uint8_t>, g4, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<uint8_t *>(origin), p->stride, p->width,
-                           p->height, d_edge_params, units_stride, sharpness, p->bit_depth);
-      else
-        hipLaunchKernelGGL(deblock_vert4_kernel<uint16_t>, g4, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<uint16_t *>(origin), p->stride, p->width,
-                           p->height, d_edge_params, units_stride, sharpness, p->bit_depth);
-      AOMHIP_LAUNCH_CHECK();
-    }
-    if (passes & 2) {
-      if (esz == 1)
-        hipLaunchKernelGGL(deblock_horz4_kernel<uint8_t>, g4, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<uint8_t *>(origin), p->stride, p->width,
-                           p->height, d_edge_params, units_stride, sharpness, p->bit_depth);
-      else
-        hipLaunchKernelGGL(deblock_horz4_kernel<uint16_t>, g4, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<uint16_t *>(origin), p->stride, p->width,
-                           p->height, d_edge_params, units_stride, sharpness, p->bit_depth);
+    const dim3 grid[2][2] = { { dim3((ucols + 63) / 64, (p->height + rows_per_wg - 1) / rows_per_wg),
+                                dim3((p->width + 63) / 64, (urows + rows_per_wg - 1) / rows_per_wg) },
+                              { g4, g4 } };
+    for (int pass = 0; pass < 2; ++pass) {
+      if (!(passes & (1 << pass))) continue;
+      hipLaunchKernelGGL(kernel[four][pass], grid[four][pass], dim3(kDbThreads), 0, ctx->stream, origin, p->stride, p->width, p->height, d_edge_params,
+                         units_stride, sharpness, p->bit_depth);
       AOMHIP_LAUNCH_CHECK();
     }
     return AOMHIP_OK;
-  }
-  if (passes & 1) {
-    if (esz == 1)
-      hipLaunchKernelGGL(deblock_vert_kernel<uint8_t>, gv, dim3(kDbThreads), 0, ctx->stream,
-                         reinterpret_cast<uint8_t *>(origin), p->stride, p->width, p->height, d_edge_params,
-                         units_stride, sharpness, p->bit_depth);
-    else
-      hipLaunchKernelGGL(deblock_vert_kernel<uint16_t>, gv, dim3(kDbThreads), 0, ctx->stream,
-                         reinterpret_cast<uint16_t *>(origin), p->stride, p->width, p->height, d_edge_params,
-                         units_stride, sharpness, p->bit_depth);
-    AOMHIP_LAUNCH_CHECK();
-  }
-  if (passes & 2) {
-    if (esz == 1)
-      hipLaunchKernelGGL(deblock_horz_kernel<uint8_t>, gh, dim3(kDbThreads), 0, ctx->stream,
-                         reinterpret_cast<uint8_t *>(origin), p->stride, p->width, p->height, d_edge_params,
-                         units_stride, sharpness, p->bit_depth);
-    else
-      hipLaunchKernelGGL(deblock_horz_kernel<uint16_t>, gh, dim3(kDbThreads), 0, ctx->stream,
-                         reinterpret_cast<uint16_t *>(origin), p->stride, p->width, p->height, d_edge_params,
-                         units_stride, sharpness, p->bit_depth);
-    AOMHIP_LAUNCH_CHECK();
-  }
-  return AOMHIP_OK;
+  });
 }
 
 int aomhip_deblock_plane_fused(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const aomhip_planes *dst, int dst_frame,
                                const uint8_t *d_edge_params, int units_stride, int sharpness) {
-  if (!ctx || !src || !dst || !src->base || !dst->base || !d_edge_params || src_frame < 0 || src_frame >= src->n_frames || dst_frame < 0 ||
-      dst_frame >= dst->n_frames || sharpness < 0 || sharpness > 7 || units_stride < (src->width + 3) / 4 || src->width != dst->width ||
-      src->height != dst->height || src->bit_depth != dst->bit_depth) {
+  if (!ctx || !valid_frame(src, src_frame) || !valid_frame(dst, dst_frame) || !d_edge_params || sharpness < 0 || sharpness > 7 ||
+      units_stride < (src->width + 3) / 4 || !same_visible(src, dst)) {
     set_error("aomhip_deblock_plane_fused: invalid argument");
     return AOMHIP_ERR_INVALID;
   }
-  if (src->base == dst->base && src_frame == dst_frame) {
+  if (same_frame(src, src_frame, dst, dst_frame)) {
     set_error("aomhip_deblock_plane_fused: source and destination must be different frames (tiles read their neighbours' unfiltered halo)");
     return AOMHIP_ERR_INVALID;
   }
@@ -669,55 +644,35 @@ int aomhip_deblock_plane_fused(aomhip_ctx *ctx, const aomhip_planes *src, int sr
     set_error("aomhip_deblock_plane_fused: the source plane needs a border of >= 8 pixels (has %d)", src->border);
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = src->bit_depth == 8 ? 1 : 2;
-  // the kernel moves tile rows as 16-byte (16-bit planes) / 4-byte (8-bit) vectors: origins, strides and frame strides of both planes must
-  // keep that alignment (aomhip_planes_alloc does; a caller-built aomhip_planes may not)
-  {
-    const size_t al = esz == 2 ? 16 : 4;
-    auto aligned = [&](const aomhip_planes *q, int f) {
-      const uintptr_t o = reinterpret_cast<uintptr_t>(q->base) + ((size_t)f * q->frame_stride + (size_t)q->border * q->stride + q->border) * esz;
-      return o % al == 0 && ((size_t)q->stride * esz) % al == 0;
-    };
-    if (!aligned(src, src_frame) || !aligned(dst, dst_frame)) {
+  return with_pixel(src->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+    const T *so = pixels<T>(src, src_frame);
+    T *dor = pixels<T>(dst, dst_frame);
+    // the kernel moves tile rows as 16-byte (16-bit planes) / 4-byte (8-bit) vectors: origins, strides and frame strides of both planes must
+    // keep that alignment (aomhip_planes_alloc does; a caller-built aomhip_planes may not)
+    const size_t al = sizeof(T) == 2 ? 16 : 4;
+    auto aligned = [&](const T *o, const aomhip_planes *q) { return reinterpret_cast<uintptr_t>(o) % al == 0 && ((size_t)q->stride * sizeof(T)) % al == 0; };
+    if (!aligned(so, src) || !aligned(dor, dst)) {
       set_error("aomhip_deblock_plane_fused: plane origin / stride not %zu-byte aligned (use aomhip_deblock_plane for such planes)", al);
       return AOMHIP_ERR_INVALID;
     }
-  }
-  const char *so = static_cast<const char *>(src->base) + ((size_t)src_frame * src->frame_stride + (size_t)src->border * src->stride + src->border) * esz;
-  char *dor = static_cast<char *>(dst->base) + ((size_t)dst_frame * dst->frame_stride + (size_t)dst->border * dst->stride + dst->border) * esz;
-  const dim3 grid((src->width + kFW - 1) / kFW, (src->height + kFH - 1) / kFH);
-  if (esz == 1)
-    hipLaunchKernelGGL(deblock_fused_kernel<uint8_t>, grid, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<const uint8_t *>(so), src->stride,
-                       reinterpret_cast<uint8_t *>(dor), dst->stride, src->width, src->height, src->border, d_edge_params, units_stride, sharpness,
-                       src->bit_depth);
-  else
-    hipLaunchKernelGGL(deblock_fused_kernel<uint16_t>, grid, dim3(kDbThreads), 0, ctx->stream, reinterpret_cast<const uint16_t *>(so), src->stride,
-                       reinterpret_cast<uint16_t *>(dor), dst->stride, src->width, src->height, src->border, d_edge_params, units_stride, sharpness,
-                       src->bit_depth);
-  AOMHIP_LAUNCH_CHECK();
-  return AOMHIP_OK;
+    hipLaunchKernelGGL(deblock_fused_kernel<T>, dim3((src->width + kFW - 1) / kFW, (src->height + kFH - 1) / kFH), dim3(kDbThreads), 0, ctx->stream, so,
+                       src->stride, dor, dst->stride, src->width, src->height, src->border, d_edge_params, units_stride, sharpness, src->bit_depth);
+    AOMHIP_LAUNCH_CHECK();
+    return AOMHIP_OK;
+  });
 }
 
 int aomhip_plane_sse(aomhip_ctx *ctx, const aomhip_planes *a, int a_frame, const aomhip_planes *b, int b_frame, uint64_t *d_sse) {
-  if (!ctx || !a || !b || !a->base || !b->base || !d_sse || a_frame < 0 || a_frame >= a->n_frames || b_frame < 0 || b_frame >= b->n_frames ||
-      a->width != b->width || a->height != b->height || a->bit_depth != b->bit_depth) {
+  if (!ctx || !valid_frame(a, a_frame) || !valid_frame(b, b_frame) || !d_sse || !same_visible(a, b)) {
     set_error("aomhip_plane_sse: invalid argument");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = a->bit_depth == 8 ? 1 : 2;
-  const char *pa = static_cast<const char *>(a->base) + ((size_t)a_frame * a->frame_stride + (size_t)a->border * a->stride + a->border) * esz;
-  const char *pb = static_cast<const char *>(b->base) + ((size_t)b_frame * b->frame_stride + (size_t)b->border * b->stride + b->border) * esz;
   if (hipMemsetAsync(d_sse, 0, sizeof(uint64_t), ctx->stream) != hipSuccess) {
     set_error("aomhip_plane_sse: memset failed");
     return AOMHIP_ERR_HIP;
   }
-  const dim3 grid((a->height + 3) / 4);   // a wavefront per row
-  if (esz == 1)
-    hipLaunchKernelGGL(plane_sse_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t *>(pa), a->stride,
-                       reinterpret_cast<const uint8_t *>(pb), b->stride, a->width, a->height, reinterpret_cast<unsigned long long *>(d_sse));
-  else
-    hipLaunchKernelGGL(plane_sse_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint16_t *>(pa), a->stride,
-                       reinterpret_cast<const uint16_t *>(pb), b->stride, a->width, a->height, reinterpret_cast<unsigned long long *>(d_sse));
+  launch_plane_sse(ctx, a, a_frame, b, b_frame, d_sse);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }
@@ -725,27 +680,20 @@ int aomhip_plane_sse(aomhip_ctx *ctx, const aomhip_planes *a, int a_frame, const
 int aomhip_lpf_search_sse(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *scratch, int scratch_frame,
                           const aomhip_planes *source, int source_frame, const uint8_t *d_edge_params, int64_t trial_stride, int n_trials,
                           int units_stride, int sharpness, int passes, uint64_t *d_sse) {
-  if (!ctx || !recon || !scratch || !source || !recon->base || !scratch->base || !source->base || !d_edge_params || n_trials <= 0 || !d_sse ||
-      recon_frame < 0 || recon_frame >= recon->n_frames || scratch_frame < 0 || scratch_frame >= scratch->n_frames || source_frame < 0 ||
-      source_frame >= source->n_frames || recon->width != scratch->width || recon->height != scratch->height ||
-      recon->stride != scratch->stride || recon->border != scratch->border || recon->frame_stride != scratch->frame_stride ||
-      recon->bit_depth != scratch->bit_depth || recon->width != source->width || recon->height != source->height ||
-      recon->bit_depth != source->bit_depth || (recon->base == scratch->base && recon_frame == scratch_frame) ||
+  if (!ctx || !valid_frame(recon, recon_frame) || !valid_frame(scratch, scratch_frame) || !valid_frame(source, source_frame) || !d_edge_params ||
+      n_trials <= 0 || !d_sse || !same_visible(recon, scratch) || recon->stride != scratch->stride || recon->border != scratch->border ||
+      recon->frame_stride != scratch->frame_stride || !same_visible(recon, source) || same_frame(recon, recon_frame, scratch, scratch_frame) ||
       trial_stride < (int64_t)units_stride * ((recon->height + 3) / 4) * 4) {
     set_error("aomhip_lpf_search_sse: invalid argument (scratch must have the reconstruction's geometry and be another frame)");
     return AOMHIP_ERR_INVALID;
   }
-  const size_t esz = recon->bit_depth == 8 ? 1 : 2;
+  const size_t esz = recon->bit_depth == 8 ? 1 : 2;   // whole frames, borders included, are copied as bytes
   const char *rframe = static_cast<const char *>(recon->base) + (size_t)recon_frame * recon->frame_stride * esz;
   char *sframe = static_cast<char *>(scratch->base) + (size_t)scratch_frame * scratch->frame_stride * esz;
-  const char *sorigin = sframe + ((size_t)scratch->border * scratch->stride + scratch->border) * esz;
-  const char *oorigin = static_cast<const char *>(source->base) +
-                        ((size_t)source_frame * source->frame_stride + (size_t)source->border * source->stride + source->border) * esz;
   if (hipMemsetAsync(d_sse, 0, sizeof(uint64_t) * (size_t)n_trials, ctx->stream) != hipSuccess) {
     set_error("aomhip_lpf_search_sse: memset failed");
     return AOMHIP_ERR_HIP;
   }
-  const dim3 grid((recon->height + 3) / 4);   // (plane_sse_kernel: a wavefront per row)
   for (int t = 0; t < n_trials; ++t) {
     // try_filter_frame (av1/encoder/picklpf.c:49-86): filter a copy, measure, and leave the unfiltered frame as it was
     if (hipMemcpyAsync(sframe, rframe, (size_t)recon->frame_stride * esz, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) {
@@ -754,14 +702,7 @@ int aomhip_lpf_search_sse(aomhip_ctx *ctx, const aomhip_planes *recon, int recon
     }
     const int rc = aomhip_deblock_plane(ctx, scratch, scratch_frame, d_edge_params + (size_t)t * trial_stride, units_stride, sharpness, passes);
     if (rc != AOMHIP_OK) return rc;
-    if (esz == 1)
-      hipLaunchKernelGGL(plane_sse_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint8_t *>(sorigin), scratch->stride,
-                         reinterpret_cast<const uint8_t *>(oorigin), source->stride, recon->width, recon->height,
-                         reinterpret_cast<unsigned long long *>(d_sse + t));
-    else
-      hipLaunchKernelGGL(plane_sse_kernel<uint16_t>, grid, dim3(256), 0, ctx->stream, reinterpret_cast<const uint16_t *>(sorigin), scratch->stride,
-                         reinterpret_cast<const uint16_t *>(oorigin), source->stride, recon->width, recon->height,
-                         reinterpret_cast<unsigned long long *>(d_sse + t));
+    launch_plane_sse(ctx, scratch, scratch_frame, source, source_frame, d_sse + t);
     AOMHIP_LAUNCH_CHECK();
   }
   return AOMHIP_OK;
@@ -781,7 +722,7 @@ void aomhip_lpf_any(void *s, int pitch, int horizontal, int len, int count, cons
     set_error("aomhip_lpf: unsupported length %d / count %d / bit depth %d", len, count, bd);
     return note_failure("aomhip_lpf", AOMHIP_ERR_INVALID);
   }
-  const int reach = len == 14 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
+  const int reach = AOMHIP_LPF_REACH(len);
   const size_t esz = is_hbd ? 2 : 1, bytes = (size_t)2 * reach * count * esz;
   char *h = static_cast<char *>(pinned(ctx, bytes)), *d = static_cast<char *>(scratch(ctx, bytes));
   if (!h || !d) return note_failure("aomhip_lpf scratch", AOMHIP_ERR_NOMEM);
