@@ -52,8 +52,7 @@ __global__ __launch_bounds__(kVarThreads) void compound_kernel(PlaneView<T> src,
   const int64_t blk = (g.pred_index ? (int64_t)g.pred_index[slot] : 0) * (W * H);
   const T *pp = KIND == kCompObmc ? nullptr : static_cast<const T *>(g.second_pred) + blk;
   const uint8_t *mp = KIND == kCompMask ? g.mask + (g.mask_offset ? g.mask_offset[slot] : 0) : nullptr;
-  static_assert(kBilinear[3][0] == 128 - 16 * 3 && kBilinear[3][1] == 16 * 3 && kBilinear[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (c.xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (c.yoff & 7) << 4, fy0 = 128 - fy1;   // (by arithmetic: a table index is a memory load)
+  const BilinearPair bfx = bilinear_pair(c.xoff), bfy = bilinear_pair(c.yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int64_t sum = 0;
   uint64_t sse = 0, sad = 0;
 #pragma unroll
@@ -76,9 +75,9 @@ __global__ __launch_bounds__(kVarThreads) void compound_kernel(PlaneView<T> src,
       load_elems<T, E>(a1 + 1, r1n);
 #pragma unroll
       for (int i = 0; i < E; ++i) {
-        const int h0 = (r0[i] * fx0 + r0n[i] * fx1 + 64) >> 7;
-        const int h1 = (r1[i] * fx0 + r1n[i] * fx1 + 64) >> 7;
-        a[i] = ((__mul24(h0, fy0) + __mul24(h1, fy1) + 64) >> 7) & (sizeof(T) == 1 ? 0xFF : 0xFFFF);
+        const int h0 = (r0[i] * bfx.f0 + r0n[i] * bfx.f1 + 64) >> 7;
+        const int h1 = (r1[i] * bfx.f0 + r1n[i] * bfx.f1 + 64) >> 7;
+        a[i] = ((__mul24(h0, bfy.f0) + __mul24(h1, bfy.f1) + 64) >> 7) & (sizeof(T) == 1 ? 0xFF : 0xFFFF);
       }
     }
     int32_t us = 0;

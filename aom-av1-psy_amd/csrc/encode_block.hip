@@ -28,7 +28,8 @@ constexpr int kEbThreads = 256;
 
 struct EbArgs {
   int ref_frame, n_blocks, nwg8;
-  int set_x, set_y, bit_depth, x_lo, x_hi, y_lo, y_hi;
+  int set_x, set_y, bit_depth;
+  PosLimits lim;
   int src_stride, rec_stride, tx_type;
 };
 
@@ -62,44 +63,24 @@ __global__ __launch_bounds__(eb_threads<W>()) void encode_inter_block_kernel(Pla
   int32_t *Q = lds[slot], *D = lds[slot] + NC, *I = lds[slot];
   const int tx_type = a.tx_type;
 
-  // ---- 1. prediction: lane = column; the W predicted pixels of the column stay in pr[] (inter_pred_kernel's walk, pred.hip)
+  // ---- 1. prediction: lane = column; the W predicted pixels of the column stay in pr[] (inter_pred_kernel's walk: pred_device.h)
   int pr[H];
   int bx = 0, by = 0;
   if (live) {
     bx = blocks[bi].bx;
     by = blocks[bi].by;
-    int pos_x = (bx << 4) + mv[2 * bi + 1] * 2, pos_y = (by << 4) + mv[2 * bi] * 2;   // init_subpel_params (reconinter.h:130-165), luma, unscaled
-    pos_x = min(max(pos_x, a.x_lo), a.x_hi);
-    pos_y = min(max(pos_y, a.y_lo), a.y_hi);
-    constexpr int tbd = BD;
-    constexpr int r0 = tbd == 12 ? 5 : 3, r1 = 14 - r0;  // get_conv_params_no_round (convolve.h:72-81)
-    constexpr int ob = tbd + 14 - r0;
-    constexpr int hoff = (1 << (tbd + 6)) + ((1 << r0) >> 1);
-    constexpr int voff = (1 << ob) + ((1 << r1) >> 1);
-    constexpr int vsub = (1 << (ob - r1)) + (1 << (ob - r1 - 1));
-    constexpr int pmax = (1 << tbd) - 1;
-    const PU128 fx = *reinterpret_cast<const PU128 *>(&kInterp[a.set_x][pos_x & 15][0]);
-    const PU128 fy = *reinterpret_cast<const PU128 *>(&kInterp[a.set_y][pos_y & 15][0]);
-    const T *p = ref.origin + (int64_t)a.ref_frame * ref.frame_stride + (int64_t)((pos_y >> 4) - 3) * ref.stride + (pos_x >> 4) - 3 + lane;
+    constexpr ConvParams cp = conv_params(BD, false);
+    const SubpelPos<T> sp = subpel_pos(ref, a.ref_frame, bx, by, mv + 2 * bi, 2, 2, a.set_x, a.set_y, a.lim);   // luma
+    const T *p = sp.base + lane;
     uint32_t win[4] = { 0, 0, 0, 0 };
 #pragma unroll
     for (int r = 0; r < H + 7; ++r) {
-      uint32_t px[4];
-      load8_pairs<T>(p, px);
+      win_push(win, conv_h8<T>(p, sp.fx, cp));
       p += ref.stride;
-      int hs = hoff;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) hs = dot2(px[k], fx.v[k], hs);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) win[k] = __builtin_amdgcn_alignbit(win[k + 1], win[k], 16);
-      win[3] = __builtin_amdgcn_alignbit((uint32_t)(hs >> r0), win[3], 16);
       if (r >= 7) {
-        int vs = voff;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) vs = dot2(win[k], fy.v[k], vs);
-        int res = (vs >> r1) - vsub;
+        int res = conv_v8(win, sp.fy, cp) - cp.vsub;
         if constexpr (!HBD) res = (int16_t)res;  // convolve.c:119 keeps it in an int16_t
-        pr[r - 7] = min(max(res, 0), pmax);
+        pr[r - 7] = min(max(res, 0), cp.pmax);
       }
     }
   } else {
@@ -246,14 +227,10 @@ int launch_eb(aomhip_ctx *ctx, const aomhip_planes *src, int src_frame, const ao
   const int nwg = (n + BPW - 1) / BPW;
   a.nwg8 = (nwg + 7) & ~7;
   a.set_x = fx; a.set_y = fy; a.bit_depth = BD;
-  // the 8-pixel row load starts 3 left of the integer position and the walk covers rows -3 .. W + 3 (pred.hip: launch_inter_pred)
-  a.x_lo = (-ref->border + 3) << 4; a.x_hi = ((ref->width + ref->border - W - 5) << 4) | 15;
-  a.y_lo = (-ref->border + 3) << 4; a.y_hi = ((ref->height + ref->border - W - 5) << 4) | 15;
+  a.lim = pos_limits(ref, ref, W, W);
   a.src_stride = src->stride; a.rec_stride = rec->stride; a.tx_type = tx_type;
-  const T *s = reinterpret_cast<const T *>(src->base) + (size_t)src_frame * src->frame_stride + (size_t)src->border * src->stride + src->border;
-  T *r = reinterpret_cast<T *>(rec->base) + (size_t)rec_frame * rec->frame_stride + (size_t)rec->border * rec->stride + rec->border;
-  hipLaunchKernelGGL((encode_inter_block_kernel<T, W, BD>), dim3(a.nwg8), dim3(eb_threads<W>()), 0, ctx->stream, view_of<T>(*ref), s, r, d_blocks, d_mv,
-                     a, qa, q, dq, eob);
+  hipLaunchKernelGGL((encode_inter_block_kernel<T, W, BD>), dim3(a.nwg8), dim3(eb_threads<W>()), 0, ctx->stream, view_of<T>(*ref),
+                     pixels<const T>(src, src_frame), pixels<T>(rec, rec_frame), d_blocks, d_mv, a, qa, q, dq, eob);
   AOMHIP_LAUNCH_CHECK();
   return AOMHIP_OK;
 }

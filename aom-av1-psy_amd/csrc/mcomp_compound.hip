@@ -15,6 +15,7 @@
 #include <climits>
 
 #include "fullpel_search.h"
+#include "pred_device.h"
 
 namespace aomhip {
 namespace {
@@ -709,23 +710,6 @@ __global__ __launch_bounds__(256) void obmc_full_pixel_search_kernel(PlaneView<T
 //   USE_8_TAPS       upsampled_obmc_pref_error (:3314-3357): aom_[highbd_]upsampled_pred = the 8-tap regular kernel of phase 2 * (mv & 7),
 //                    horizontal then vertical pass, each rounded and clipped (taps 0 and 7 are zero in every phase: six taps), then vfp->ovf,
 //                    + mv_err_cost_
-__device__ constexpr int16_t kObmcSubPel8[16][6] = {   // av1_sub_pel_filters_8 (av1/common/filter.h:124-141), taps 1 .. 6
-  { 0, 0, 128, 0, 0, 0 },      { 2, -6, 126, 8, -2, 0 },    { 2, -10, 122, 18, -4, 0 },  { 2, -12, 116, 28, -8, 2 },
-  { 2, -14, 110, 38, -10, 2 }, { 2, -14, 102, 48, -12, 2 }, { 2, -16, 94, 58, -12, 2 },  { 2, -14, 84, 66, -12, 2 },
-  { 2, -14, 76, 76, -14, 2 },  { 2, -12, 66, 84, -14, 2 },  { 2, -12, 58, 94, -16, 2 },  { 2, -12, 48, 102, -14, 2 },
-  { 2, -10, 38, 110, -14, 2 }, { 2, -8, 28, 116, -12, 2 },  { 0, -4, 18, 122, -10, 2 },  { 0, -2, 8, 126, -6, 2 }
-};
-__device__ constexpr int16_t kObmcSubPel4[16][6] = {   // av1_sub_pel_filters_4 (filter.h:205-215; USE_4_TAPS, av1_get_filter :270-279), taps 1 .. 6
-  { 0, 0, 128, 0, 0, 0 },     { 0, -4, 126, 8, -2, 0 },   { 0, -8, 122, 18, -4, 0 },  { 0, -10, 116, 28, -6, 0 },
-  { 0, -12, 110, 38, -8, 0 }, { 0, -12, 102, 48, -10, 0 }, { 0, -14, 94, 58, -10, 0 }, { 0, -12, 84, 66, -10, 0 },
-  { 0, -12, 76, 76, -12, 0 }, { 0, -10, 66, 84, -12, 0 }, { 0, -10, 58, 94, -14, 0 }, { 0, -10, 48, 102, -12, 0 },
-  { 0, -8, 38, 110, -12, 0 }, { 0, -6, 28, 116, -10, 0 }, { 0, -4, 18, 122, -8, 0 },  { 0, -2, 8, 126, -4, 0 }
-};
-// tap k + 1 of the kernel of phase ph (0 .. 15) under SUBPEL_SEARCH_TYPE type: 1 USE_2_TAPS = av1_bilinear_filters, 2 USE_4_TAPS, 3 USE_8_TAPS
-__device__ __forceinline__ int obmc_up_tap(int type, int ph, int k) {
-  if (type == 1) return k == 2 ? 128 - 8 * ph : (k == 3 ? 8 * ph : 0);
-  return type == 2 ? kObmcSubPel4[ph][k] : kObmcSubPel8[ph][k];
-}
 struct ObmcSubpelArgs { int iters_per_step, allow_hp, forced_stop, upsampled; };   // upsampled: 0, or the SUBPEL_SEARCH_TYPE (1 / 2 / 3)
 
 template <typename T>
@@ -747,20 +731,18 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
   const int32_t *wsrc = wsrc_all + (size_t)bi * n_px, *omask = omask_all + (size_t)bi * n_px;
   const int pmax = sizeof(T) == 1 ? 255 : (1 << a.bit_depth) - 1;
   const int lw_ = __builtin_ctz((unsigned)W);
-  constexpr uint8_t kBil[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 }, { 64, 64 }, { 48, 80 }, { 32, 96 }, { 16, 112 } };  // aom_filter.h:43-50
   // the up-sampling kernel's tap pairs (taps 2 k, 2 k + 1 of the six) of the eight 1/8-pel phases, one per lane: lane = 3 * phase + k.  (Looked
-  // up per candidate through obmc_up_tap they were twelve table reads on the scalar unit, which bounds this kernel: PMC r05e.)
+  // up per candidate through up_tap they were twelve table reads on the scalar unit, which bounds this kernel: PMC r05e.)
   int tap_l = 0;
   if (sa.upsampled && lane < 24) {
     const int ph = 2 * (lane / 3), k = lane % 3;
-    tap_l = (int)(((uint32_t)(uint16_t)(int16_t)obmc_up_tap(sa.upsampled, ph, 2 * k)) | ((uint32_t)(uint16_t)(int16_t)obmc_up_tap(sa.upsampled, ph, 2 * k + 1) << 16));
+    tap_l = (int)(((uint32_t)(uint16_t)(int16_t)up_tap(sa.upsampled, ph, 2 * k)) | ((uint32_t)(uint16_t)(int16_t)up_tap(sa.upsampled, ph, 2 * k + 1) << 16));
   }
   // obmc_variance of the prediction at (mrow, mcol): form 0 = the plain block at the full-pel part (ovf), 1 = bilinear (osvf), 2 = up-sampled
   auto obmc_err = [&](int mrow, int mcol, int form, uint32_t *sse_out) -> uint32_t {
     const T *rp = rbase + (int64_t)(mrow >> 3) * ref.stride + (mcol >> 3);
     const int sx = mcol & 7, sy = mrow & 7;
-    static_assert(kBil[3][0] == 128 - 16 * 3 && kBil[3][1] == 16 * 3 && kBil[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-    const int fx1 = (sx & 7) << 4, fx0 = 128 - fx1, fy1 = (sy & 7) << 4, fy0 = 128 - fy1;   // (by arithmetic: a table index is a memory load)
+    const BilinearPair bfx = bilinear_pair(sx), bfy = bilinear_pair(sy);   // by arithmetic: a table index is a memory load on every candidate's chain
     int64_t s = 0, q = 0;
     if (form == 2) {
       // The up-sampled form in two passes through the wavefront's LDS tile, a lane taking units of four adjacent pixels: the horizontal pass
@@ -873,16 +855,16 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
       if (form == 0) {
         pv = (int)p[0];
       } else if (form == 1) {   // aom_var_filter_block2d_bil_first_pass / _second_pass
-        const int h0 = ((int)p[0] * fx0 + (int)p[1] * fx1 + 64) >> 7;
-        const int h1 = ((int)p[ref.stride] * fx0 + (int)p[ref.stride + 1] * fx1 + 64) >> 7;
-        pv = (h0 * fy0 + h1 * fy1 + 64) >> 7;
+        const int h0 = ((int)p[0] * bfx.f0 + (int)p[1] * bfx.f1 + 64) >> 7;
+        const int h1 = ((int)p[ref.stride] * bfx.f0 + (int)p[ref.stride + 1] * bfx.f1 + 64) >> 7;
+        pv = (h0 * bfy.f0 + h1 * bfy.f1 + 64) >> 7;
       } else {
         auto hrow = [&](int dy) -> int {   // the horizontal pass at row y + dy
           const T *r = p + (int64_t)dy * ref.stride;
           if (!sx) return (int)r[0];
           int sum = 0;
 #pragma unroll
-          for (int k = 0; k < 6; ++k) sum += (int)r[k - 2] * obmc_up_tap(sa.upsampled, 2 * sx, k);
+          for (int k = 0; k < 6; ++k) sum += (int)r[k - 2] * up_tap(sa.upsampled, 2 * sx, k);
           return min(max((sum + 64) >> 7, 0), pmax);
         };
         if (!sy) {
@@ -890,7 +872,7 @@ __global__ __launch_bounds__(256) void obmc_subpel_tree_kernel(PlaneView<T> ref,
         } else {
           int sum = 0;
 #pragma unroll
-          for (int k = 0; k < 6; ++k) sum += hrow(k - 2) * obmc_up_tap(sa.upsampled, 2 * sy, k);
+          for (int k = 0; k < 6; ++k) sum += hrow(k - 2) * up_tap(sa.upsampled, 2 * sy, k);
           pv = min(max((sum + 64) >> 7, 0), pmax);
         }
       }

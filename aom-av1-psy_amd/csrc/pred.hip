@@ -35,50 +35,25 @@ __global__ __launch_bounds__(256) void inter_pred_kernel(PlaneView<T> ref, int r
   if (bi >= n_blocks) return;
   const int col0 = lane % LPB;
   const int bx = blocks[bi].bx, by = blocks[bi].by;
-  // init_subpel_params (reconinter.h:130-165), unscaled: position in 1/16 pel, mv * (1 << (1 - subsampling))
-  int pos_x = (bx << 4) + mv[2 * bi + 1] * mvx_mul, pos_y = (by << 4) + mv[2 * bi] * mvy_mul;
-  // keeps every access inside the allocation; the identity for MVs within av1_set_mv_limits (mcomp.h:216-247)
-  pos_x = min(max(pos_x, x_lo), x_hi);
-  pos_y = min(max(pos_y, y_lo), y_hi);
-  const int tbd = sizeof(T) == 1 ? 8 : bit_depth;
-  const int r0 = tbd == 12 ? 5 : 3, r1 = 14 - r0;  // get_conv_params_no_round (convolve.h:72-81)
-  const int ob = tbd + 14 - r0;
-  const int hoff = (1 << (tbd + 6)) + ((1 << r0) >> 1);
-  const int voff = (1 << ob) + ((1 << r1) >> 1);
-  const int vsub = (1 << (ob - r1)) + (1 << (ob - r1 - 1));
-  const int pmax = (1 << tbd) - 1;
-  // the kernels as four (tap 2k, tap 2k + 1) pairs each: exactly the table's memory layout
-  const PU128 fx = *reinterpret_cast<const PU128 *>(&kInterp[set_x][pos_x & 15][0]);
-  const PU128 fy = *reinterpret_cast<const PU128 *>(&kInterp[set_y][pos_y & 15][0]);
-  const T *base = ref.origin + (int64_t)ref_frame * ref.frame_stride + (int64_t)((pos_y >> 4) - 3) * ref.stride + (pos_x >> 4) - 3;
+  const ConvParams cp = conv_params(sizeof(T) == 1 ? 8 : bit_depth, false);
+  const SubpelPos<T> sp = subpel_pos(ref, ref_frame, bx, by, mv + 2 * bi, mvx_mul, mvy_mul, set_x, set_y, PosLimits{ x_lo, x_hi, y_lo, y_hi });
   // dst_stride 0: block i contiguous at dst_origin + i * W * H (the second_pred layout of the compound searches)
   T *dbase = dst_stride ? dst_origin + (int64_t)by * dst_stride + bx : dst_origin + (int64_t)bi * (W * H);
   if (!dst_stride) dst_stride = W;
 #pragma unroll 1
   for (int col = col0; col < W; col += 64) {
-    const T *p = base + col;
+    const T *p = sp.base + col;
     T *d = dbase + col;
-    // the last 8 intermediates as four 16-bit pairs (they fit 15 bits: convolve.h:76-81 sizes round_0 for that)
     uint32_t win[4] = { 0, 0, 0, 0 };
 #pragma unroll 8
     for (int r = 0; r < H + 7; ++r) {
-      uint32_t px[4];
-      load8_pairs<T>(p, px);
+      win_push(win, conv_h8<T>(p, sp.fx, cp));
       p += ref.stride;
-      int hs = hoff;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) hs = dot2(px[k], fx.v[k], hs);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) win[k] = __builtin_amdgcn_alignbit(win[k + 1], win[k], 16);
-      win[3] = __builtin_amdgcn_alignbit((uint32_t)(hs >> r0), win[3], 16);
       if (r >= 7) {
-        int vs = voff;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) vs = dot2(win[k], fy.v[k], vs);
-        int res = (vs >> r1) - vsub;
+        int res = conv_v8(win, sp.fy, cp) - cp.vsub;
         if constexpr (sizeof(T) == 1) res = (int16_t)res;  // convolve.c:119 keeps it in an int16_t
         // bits = 14 - round_0 - round_1 == 0: ROUND_POWER_OF_TWO(res, 0) is res
-        *d = (T)min(max(res, 0), pmax);
+        *d = (T)min(max(res, 0), cp.pmax);
         d += dst_stride;
       }
     }
@@ -107,68 +82,35 @@ __global__ __launch_bounds__(256) void compound_pred_kernel(PlaneView<T> ref0, i
   const int col0 = lane % LPB;
   const int bx = blocks[bi].bx, by = blocks[bi].by;
   const uint8_t *mk = mask ? mask + (mask_offset ? mask_offset[bi] : 0) : nullptr;
-  int px0 = (bx << 4) + mv0[2 * bi + 1] * mvx_mul, py0 = (by << 4) + mv0[2 * bi] * mvy_mul;
-  int px1 = (bx << 4) + mv1[2 * bi + 1] * mvx_mul, py1 = (by << 4) + mv1[2 * bi] * mvy_mul;
-  px0 = min(max(px0, x_lo), x_hi); py0 = min(max(py0, y_lo), y_hi);
-  px1 = min(max(px1, x_lo), x_hi); py1 = min(max(py1, y_lo), y_hi);
   const int tbd = sizeof(T) == 1 ? 8 : bit_depth;
-  const int r0 = tbd == 12 ? 5 : 3, r1 = 7;           // get_conv_params_no_round, is_compound (convolve.h:72-81)
-  const int ob = tbd + 14 - r0;
-  const int hoff = (1 << (tbd + 6)) + ((1 << r0) >> 1);
-  const int voff = (1 << ob) + ((1 << r1) >> 1);
-  const int round_offset = (1 << (ob - r1)) + (1 << (ob - r1 - 1));
-  const int rb = 14 - r0 - r1;                         // round_bits: 4, or 2 for 12-bit
-  const int pmax = (1 << tbd) - 1;
-  const PU128 fx0 = *reinterpret_cast<const PU128 *>(&kInterp[set_x][px0 & 15][0]);
-  const PU128 fy0 = *reinterpret_cast<const PU128 *>(&kInterp[set_y][py0 & 15][0]);
-  const PU128 fx1 = *reinterpret_cast<const PU128 *>(&kInterp[set_x][px1 & 15][0]);
-  const PU128 fy1 = *reinterpret_cast<const PU128 *>(&kInterp[set_y][py1 & 15][0]);
-  const T *b0 = ref0.origin + (int64_t)frame0 * ref0.frame_stride + (int64_t)((py0 >> 4) - 3) * ref0.stride + (px0 >> 4) - 3;
-  const T *b1 = ref1.origin + (int64_t)frame1 * ref1.frame_stride + (int64_t)((py1 >> 4) - 3) * ref1.stride + (px1 >> 4) - 3;
+  const ConvParams cp = conv_params(tbd, true);
+  const PosLimits lim{ x_lo, x_hi, y_lo, y_hi };
+  const SubpelPos<T> s0 = subpel_pos(ref0, frame0, bx, by, mv0 + 2 * bi, mvx_mul, mvy_mul, set_x, set_y, lim);
+  const SubpelPos<T> s1 = subpel_pos(ref1, frame1, bx, by, mv1 + 2 * bi, mvx_mul, mvy_mul, set_x, set_y, lim);
   T *dbase = dst_origin + (int64_t)by * dst_stride + bx;
 #pragma unroll 1
   for (int col = col0; col < W; col += 64) {
-    const T *p0 = b0 + col, *p1 = b1 + col;
+    const T *p0 = s0.base + col, *p1 = s1.base + col;
     T *d = dbase + col;
     uint32_t w0[4] = { 0, 0, 0, 0 }, w1[4] = { 0, 0, 0, 0 };
 #pragma unroll 4
     for (int r = 0; r < H + 7; ++r) {
-      uint32_t a[4], b[4];
-      load8_pairs<T>(p0, a);
-      load8_pairs<T>(p1, b);
+      const uint32_t h0 = conv_h8<T>(p0, s0.fx, cp), h1 = conv_h8<T>(p1, s1.fx, cp);
       p0 += ref0.stride;
       p1 += ref1.stride;
-      int h0 = hoff, h1 = hoff;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        h0 = dot2(a[k], fx0.v[k], h0);
-        h1 = dot2(b[k], fx1.v[k], h1);
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        w0[k] = __builtin_amdgcn_alignbit(w0[k + 1], w0[k], 16);
-        w1[k] = __builtin_amdgcn_alignbit(w1[k + 1], w1[k], 16);
-      }
-      w0[3] = __builtin_amdgcn_alignbit((uint32_t)(h0 >> r0), w0[3], 16);
-      w1[3] = __builtin_amdgcn_alignbit((uint32_t)(h1 >> r0), w1[3], 16);
+      win_push(w0, h0);
+      win_push(w1, h1);
       if (r >= 7) {
-        int v0 = voff, v1 = voff;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          v0 = dot2(w0[k], fy0.v[k], v0);
-          v1 = dot2(w1[k], fy1.v[k], v1);
-        }
-        const int res0 = v0 >> r1, res1 = v1 >> r1;   // the two CONV_BUF values (fit 16 bits)
-        // convolve.c:222-233: distance weights (sum 16) or the plain average, then the offset comes out and the result is rounded
-        int tmp;
+        const int res0 = conv_v8(w0, s0.fy, cp), res1 = conv_v8(w1, s1.fy, cp);   // the two CONV_BUF values (fit 16 bits)
+        int px;
         if (diffwtd) {  // av1_build_compound_diffwtd_mask_d16 (reconinter.c:296-328): the mask comes from the two predictors
-          const int rnd = rb + tbd - 8;
+          const int rnd = cp.round_bits + tbd - 8;
           int diff = res0 > res1 ? res0 - res1 : res1 - res0;
           diff = (diff + ((1 << rnd) >> 1)) >> rnd;
           int m = min(38 + (diff >> 4), 64);   // DIFF_FACTOR 16; never below 38
           m = diffwtd == 2 ? 64 - m : m;
           if (mask_out) mask_out[((int64_t)bi * H + (r - 7)) * W + col] = (uint8_t)m;
-          tmp = (m * res0 + (64 - m) * res1) >> 6;
+          px = conv_to_pixel((m * res0 + (64 - m) * res1) >> 6, cp);
         } else if (mk) {  // aom_[lowbd|highbd]_blend_a64_d16_mask (aom_dsp/blend_a64_mask.c): the mask weighs reference 0
           const int y = r - 7;
           const uint8_t *mr = mk + (y << subh) * mask_stride + (col << subw);
@@ -176,13 +118,11 @@ __global__ __launch_bounds__(256) void compound_pred_kernel(PlaneView<T> ref0, i
           if (subw & subh) m = (m + mr[1] + mr[mask_stride] + mr[mask_stride + 1] + 2) >> 2;
           else if (subw) m = (m + mr[1] + 1) >> 1;
           else if (subh) m = (m + mr[mask_stride] + 1) >> 1;
-          tmp = (m * res0 + (64 - m) * res1) >> 6;
+          px = conv_to_pixel((m * res0 + (64 - m) * res1) >> 6, cp);
         } else {
-          tmp = fwd | bck ? (res0 * fwd + res1 * bck) >> 4 : (res0 + res1) >> 1;
+          px = compound_finish(res0, res1, fwd | bck, fwd, bck, cp);
         }
-        tmp -= round_offset;
-        tmp = (tmp + ((1 << rb) >> 1)) >> rb;
-        *d = (T)min(max(tmp, 0), pmax);
+        *d = (T)px;
         d += dst_stride;
       }
     }
@@ -229,36 +169,36 @@ __global__ __launch_bounds__(256) void pred_copy_kernel(PlaneView<T> ref, int re
 }
 
 
-#define AOMHIP_PRED_SIZES(X)                                                                                     \
-  X(4, 4) X(4, 8) X(8, 4) X(8, 8) X(8, 16) X(16, 8) X(16, 16) X(16, 32) X(32, 16) X(32, 32) X(32, 64) X(64, 32) \
-  X(64, 64) X(64, 128) X(128, 64) X(128, 128) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
+static int invalid(const char *who, const char *what = "invalid argument") {
+  set_error("%s: %s", who, what);
+  return AOMHIP_ERR_INVALID;
+}
+constexpr const char *kBorderMsg = "the reference planes need a border of at least 8 pixels for the 8-tap kernels";
+static bool filters_ok(int fx, int fy) { return fx >= 0 && fx <= 3 && fy >= 0 && fy <= 3; }
+static bool subsampling_ok(int ss_x, int ss_y) { return ss_x >= 0 && ss_x <= 1 && ss_y >= 0 && ss_y <= 1; }
 
-template <typename T>
-static int launch_inter_pred(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred, int pred_frame, int bw,
-                             int bh, const aomhip_search_block *d_blocks, const int16_t *d_mv, int n_blocks, int fx, int fy, int ss_x, int ss_y,
+// d_contiguous: block i at d_contiguous + i * bw * bh (the second_pred layout of the compound searches) and no prediction ring
+static int launch_inter_pred(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred, int pred_frame, int bw, int bh,
+                             const aomhip_search_block *d_blocks, const int16_t *d_mv, int n_blocks, int fx, int fy, int ss_x, int ss_y,
                              void *d_contiguous = nullptr) {
-  // av1_get_interp_filter_params_with_block_size (filter.h:247-253): a dimension <= 4 takes the 4-tap sets
-  auto set_of = [](int f, int dim) { return dim <= 4 ? (f == 1 ? 5 : f == 3 ? 3 : 4) : f; };
-  T *d = d_contiguous ? static_cast<T *>(d_contiguous)
-                      : reinterpret_cast<T *>(pred->base) + (size_t)pred_frame * pred->frame_stride + (size_t)pred->border * pred->stride + pred->border;
-  const int dst_stride = d_contiguous ? 0 : pred->stride;
-  // the 8-pixel row load starts 3 left of the integer position and the walk covers rows -3 .. bh + 3
-  const int x_lo = (-ref->border + 3) << 4, x_hi = ((ref->width + ref->border - bw - 5) << 4) | 15;
-  const int y_lo = (-ref->border + 3) << 4, y_hi = ((ref->height + ref->border - bh - 5) << 4) | 15;
+  const PosLimits lim = pos_limits(ref, ref, bw, bh);
   const int lpb = bw < 64 ? bw : 64, bpw = 64 / lpb;
   const dim3 grid((n_blocks + 4 * bpw - 1) / (4 * bpw)), block(256);
-#define X(W, H)                                                                                                                    \
-  if (bw == W && bh == H) {                                                                                                        \
-    hipLaunchKernelGGL((inter_pred_kernel<T, W, H>), grid, block, 0, ctx->stream, view_of<T>(*ref), ref_frame, d, dst_stride,     \
-                       d_blocks, d_mv, n_blocks, set_of(fx, W), set_of(fy, H), ref->bit_depth, x_lo, x_hi, y_lo, y_hi, 2 >> ss_x,  \
-                       2 >> ss_y);                                                                                                 \
-    AOMHIP_LAUNCH_CHECK();                                                                                                         \
-    return AOMHIP_OK;                                                                                                              \
+  return with_pixel(ref->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+    T *d = d_contiguous ? static_cast<T *>(d_contiguous) : pixels<T>(pred, pred_frame);
+#define X(W, H)                                                                                                                                        \
+  if (bw == W && bh == H) {                                                                                                                            \
+    hipLaunchKernelGGL((inter_pred_kernel<T, W, H>), grid, block, 0, ctx->stream, view_of<T>(*ref), ref_frame, d, d_contiguous ? 0 : pred->stride,    \
+                       d_blocks, d_mv, n_blocks, interp_set(fx, W), interp_set(fy, H), ref->bit_depth, lim.x_lo, lim.x_hi, lim.y_lo, lim.y_hi, \
+                       2 >> ss_x, 2 >> ss_y);                                                                                                          \
+    AOMHIP_LAUNCH_CHECK();                                                                                                                             \
+    return AOMHIP_OK;                                                                                                                                  \
   }
-  AOMHIP_PRED_SIZES(X)
+    AOMHIP_FOR_BLOCK_SIZES(X)
 #undef X
-  set_error("unsupported block size %dx%d", bw, bh);
-  return AOMHIP_ERR_INVALID;
+    return invalid("inter prediction", "unsupported block size");   // (not reached: the entry points check valid_block)
+  });
 }
 
 }  // namespace aomhip
@@ -268,41 +208,25 @@ using namespace aomhip;
 extern "C" int aomhip_build_inter_pred_ex_batch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred,
                                                 int pred_frame, int bw, int bh, const aomhip_search_block *d_blocks, const int16_t *d_mv,
                                                 int n_blocks, int interp_filter_x, int interp_filter_y, int subsampling_x, int subsampling_y) {
-  if (!ctx || !ref || !pred || !ref->base || !pred->base || (n_blocks > 0 && (!d_blocks || !d_mv)) || n_blocks < 0 || ref_frame < 0 ||
-      ref_frame >= ref->n_frames || pred_frame < 0 || pred_frame >= pred->n_frames || !valid_block(bw, bh) ||
-      ref->bit_depth != pred->bit_depth || interp_filter_x < 0 || interp_filter_x > 3 || interp_filter_y < 0 || interp_filter_y > 3 ||
-      subsampling_x < 0 || subsampling_x > 1 || subsampling_y < 0 || subsampling_y > 1) {
-    set_error("aomhip_build_inter_pred_batch: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (ref->border < 8) {
-    set_error("aomhip_build_inter_pred_batch: the reference planes need a border of at least 8 pixels for the 8-tap kernels");
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!ctx || !valid_frame(ref, ref_frame) || !valid_frame(pred, pred_frame) || (n_blocks > 0 && (!d_blocks || !d_mv)) || n_blocks < 0 ||
+      !valid_block(bw, bh) || ref->bit_depth != pred->bit_depth || !filters_ok(interp_filter_x, interp_filter_y) ||
+      !subsampling_ok(subsampling_x, subsampling_y))
+    return invalid("aomhip_build_inter_pred_batch");
+  if (ref->border < 8) return invalid("aomhip_build_inter_pred_batch", kBorderMsg);
   if (n_blocks == 0) return AOMHIP_OK;
-  if (ref->bit_depth == 8)
-    return launch_inter_pred<uint8_t>(ctx, ref, ref_frame, pred, pred_frame, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y,
-                                      subsampling_x, subsampling_y);
-  return launch_inter_pred<uint16_t>(ctx, ref, ref_frame, pred, pred_frame, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y,
-                                     subsampling_x, subsampling_y);
+  return launch_inter_pred(ctx, ref, ref_frame, pred, pred_frame, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y, subsampling_x,
+                           subsampling_y);
 }
 
 extern "C" int aomhip_build_inter_pred_contiguous_batch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, void *d_pred, int bw, int bh,
                                                         const aomhip_search_block *d_blocks, const int16_t *d_mv, int n_blocks, int interp_filter_x,
                                                         int interp_filter_y) {
-  if (!ctx || !ref || !ref->base || !d_pred || (n_blocks > 0 && (!d_blocks || !d_mv)) || n_blocks < 0 || ref_frame < 0 || ref_frame >= ref->n_frames ||
-      !valid_block(bw, bh) || interp_filter_x < 0 || interp_filter_x > 3 || interp_filter_y < 0 || interp_filter_y > 3) {
-    set_error("aomhip_build_inter_pred_contiguous_batch: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (ref->border < 8) {
-    set_error("aomhip_build_inter_pred_contiguous_batch: the reference planes need a border of at least 8 pixels for the 8-tap kernels");
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!ctx || !valid_frame(ref, ref_frame) || !d_pred || (n_blocks > 0 && (!d_blocks || !d_mv)) || n_blocks < 0 || !valid_block(bw, bh) ||
+      !filters_ok(interp_filter_x, interp_filter_y))
+    return invalid("aomhip_build_inter_pred_contiguous_batch");
+  if (ref->border < 8) return invalid("aomhip_build_inter_pred_contiguous_batch", kBorderMsg);
   if (n_blocks == 0) return AOMHIP_OK;
-  if (ref->bit_depth == 8)
-    return launch_inter_pred<uint8_t>(ctx, ref, ref_frame, nullptr, 0, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y, 0, 0, d_pred);
-  return launch_inter_pred<uint16_t>(ctx, ref, ref_frame, nullptr, 0, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y, 0, 0, d_pred);
+  return launch_inter_pred(ctx, ref, ref_frame, nullptr, 0, bw, bh, d_blocks, d_mv, n_blocks, interp_filter_x, interp_filter_y, 0, 0, d_pred);
 }
 
 extern "C" int aomhip_build_inter_pred_batch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred,
@@ -312,31 +236,54 @@ extern "C" int aomhip_build_inter_pred_batch(aomhip_ctx *ctx, const aomhip_plane
                                           interp_filter_y, 0, 0);
 }
 
-template <typename T>
-static int launch_compound_pred(aomhip_ctx *ctx, const aomhip_planes *r0, int f0, const aomhip_planes *r1, int f1, const aomhip_planes *pred,
-                                int pred_frame, int bw, int bh, const aomhip_search_block *d_blocks, const int16_t *mv0, const int16_t *mv1,
-                                int n_blocks, int fx, int fy, int fwd, int bck, int ss_x, int ss_y, const uint8_t *mask = nullptr,
-                                const uint32_t *mask_offset = nullptr, int mask_stride = 0, int subw = 0, int subh = 0, int diffwtd = 0,
-                                uint8_t *mask_out = nullptr) {
-  auto set_of = [](int f, int dim) { return dim <= 4 ? (f == 1 ? 5 : f == 3 ? 3 : 4) : f; };
-  T *d = reinterpret_cast<T *>(pred->base) + (size_t)pred_frame * pred->frame_stride + (size_t)pred->border * pred->stride + pred->border;
-  const int border = r0->border < r1->border ? r0->border : r1->border;
-  const int x_lo = (-border + 3) << 4, x_hi = ((r0->width + border - bw - 5) << 4) | 15;
-  const int y_lo = (-border + 3) << 4, y_hi = ((r0->height + border - bh - 5) << 4) | 15;
-  const int lpb = bw < 64 ? bw : 64, bpw = 64 / lpb;
-  const dim3 grid((n_blocks + 4 * bpw - 1) / (4 * bpw)), block(256);
-#define X(W, H)                                                                                                                        \
-  if (bw == W && bh == H) {                                                                                                            \
-    hipLaunchKernelGGL((compound_pred_kernel<T, W, H>), grid, block, 0, ctx->stream, view_of<T>(*r0), f0, view_of<T>(*r1), f1, d,      \
-                       pred->stride, d_blocks, mv0, mv1, n_blocks, set_of(fx, W), set_of(fy, H), r0->bit_depth, x_lo, x_hi, y_lo, y_hi, \
-                       2 >> ss_x, 2 >> ss_y, fwd, bck, mask, mask_offset, mask_stride, subw, subh, diffwtd, mask_out);                  \
-    AOMHIP_LAUNCH_CHECK();                                                                                                             \
-    return AOMHIP_OK;                                                                                                                  \
+// The three compound entry points' common arguments and what they all require of them: valid frames, lists where there are blocks, a block size,
+// one bit depth, references of one visible size with borders for the 8-tap kernels, filters 0 .. 3
+struct CompoundCall {
+  aomhip_ctx *ctx;
+  const aomhip_planes *ref0;
+  int ref0_frame;
+  const aomhip_planes *ref1;
+  int ref1_frame;
+  const aomhip_planes *pred;
+  int pred_frame, bw, bh;
+  const aomhip_search_block *d_blocks;
+  const int16_t *d_mv0, *d_mv1;
+  int n_blocks, fx, fy;
+  bool ok() const {
+    return ctx && valid_frame(ref0, ref0_frame) && valid_frame(ref1, ref1_frame) && valid_frame(pred, pred_frame) &&
+           !(n_blocks > 0 && (!d_blocks || !d_mv0 || !d_mv1)) && n_blocks >= 0 && valid_block(bw, bh) && ref0->bit_depth == pred->bit_depth &&
+           ref1->bit_depth == pred->bit_depth && ref0->width == ref1->width && ref0->height == ref1->height && filters_ok(fx, fy) &&
+           ref0->border >= 8 && ref1->border >= 8;
   }
-  AOMHIP_PRED_SIZES(X)
+};
+struct CompoundBlend {   // at most one of: distance weights, a mask (weighing reference 0), the mask derived from the two predictors (diffwtd 1 / 2)
+  int fwd = 0, bck = 0;
+  const uint8_t *mask = nullptr;
+  const uint32_t *mask_offset = nullptr;
+  int mask_stride = 0, subw = 0, subh = 0, diffwtd = 0;
+  uint8_t *mask_out = nullptr;
+};
+
+static int launch_compound_pred(const CompoundCall &c, int ss_x, int ss_y, const CompoundBlend &b) {
+  if (c.n_blocks == 0) return AOMHIP_OK;
+  const PosLimits lim = pos_limits(c.ref0, c.ref1, c.bw, c.bh);
+  const int lpb = c.bw < 64 ? c.bw : 64, bpw = 64 / lpb;
+  const dim3 grid((c.n_blocks + 4 * bpw - 1) / (4 * bpw)), block(256);
+  return with_pixel(c.pred->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+#define X(W, H)                                                                                                                                       \
+  if (c.bw == W && c.bh == H) {                                                                                                                       \
+    hipLaunchKernelGGL((compound_pred_kernel<T, W, H>), grid, block, 0, c.ctx->stream, view_of<T>(*c.ref0), c.ref0_frame, view_of<T>(*c.ref1),       \
+                       c.ref1_frame, pixels<T>(c.pred, c.pred_frame), c.pred->stride, c.d_blocks, c.d_mv0, c.d_mv1, c.n_blocks,                      \
+                       interp_set(c.fx, W), interp_set(c.fy, H), c.ref0->bit_depth, lim.x_lo, lim.x_hi, lim.y_lo, lim.y_hi, 2 >> ss_x,         \
+                       2 >> ss_y, b.fwd, b.bck, b.mask, b.mask_offset, b.mask_stride, b.subw, b.subh, b.diffwtd, b.mask_out);                         \
+    AOMHIP_LAUNCH_CHECK();                                                                                                                            \
+    return AOMHIP_OK;                                                                                                                                 \
+  }
+    AOMHIP_FOR_BLOCK_SIZES(X)
 #undef X
-  set_error("unsupported block size %dx%d", bw, bh);
-  return AOMHIP_ERR_INVALID;
+    return invalid("compound prediction", "unsupported block size");   // (not reached: ok() checks valid_block)
+  });
 }
 
 extern "C" int aomhip_build_compound_pred_batch(aomhip_ctx *ctx, const aomhip_planes *ref0, int ref0_frame, const aomhip_planes *ref1,
@@ -344,21 +291,13 @@ extern "C" int aomhip_build_compound_pred_batch(aomhip_ctx *ctx, const aomhip_pl
                                                 const aomhip_search_block *d_blocks, const int16_t *d_mv0, const int16_t *d_mv1, int n_blocks,
                                                 int interp_filter_x, int interp_filter_y, int fwd_offset, int bck_offset, int subsampling_x,
                                                 int subsampling_y) {
-  if (!ctx || !ref0 || !ref1 || !pred || !ref0->base || !ref1->base || !pred->base || (n_blocks > 0 && (!d_blocks || !d_mv0 || !d_mv1)) ||
-      n_blocks < 0 || ref0_frame < 0 || ref0_frame >= ref0->n_frames || ref1_frame < 0 || ref1_frame >= ref1->n_frames || pred_frame < 0 ||
-      pred_frame >= pred->n_frames || !valid_block(bw, bh) || ref0->bit_depth != pred->bit_depth || ref1->bit_depth != pred->bit_depth ||
-      ref0->width != ref1->width || ref0->height != ref1->height || interp_filter_x < 0 || interp_filter_x > 3 || interp_filter_y < 0 ||
-      interp_filter_y > 3 || subsampling_x < 0 || subsampling_x > 1 || subsampling_y < 0 || subsampling_y > 1 || fwd_offset < 0 ||
-      bck_offset < 0 || ((fwd_offset | bck_offset) && fwd_offset + bck_offset != 16) || ref0->border < 8 || ref1->border < 8) {
-    set_error("aomhip_build_compound_pred_batch: invalid argument (weights 0 / 0 or summing to 16; reference borders >= 8)");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (n_blocks == 0) return AOMHIP_OK;
-  if (pred->bit_depth == 8)
-    return launch_compound_pred<uint8_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                         interp_filter_x, interp_filter_y, fwd_offset, bck_offset, subsampling_x, subsampling_y);
-  return launch_compound_pred<uint16_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                        interp_filter_x, interp_filter_y, fwd_offset, bck_offset, subsampling_x, subsampling_y);
+  const CompoundCall c{ ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks, interp_filter_x, interp_filter_y };
+  if (!c.ok() || !subsampling_ok(subsampling_x, subsampling_y) || fwd_offset < 0 || bck_offset < 0 ||
+      ((fwd_offset | bck_offset) && fwd_offset + bck_offset != 16))
+    return invalid("aomhip_build_compound_pred_batch", "invalid argument (weights 0 / 0 or summing to 16; reference borders >= 8)");
+  CompoundBlend b;
+  b.fwd = fwd_offset, b.bck = bck_offset;
+  return launch_compound_pred(c, subsampling_x, subsampling_y, b);
 }
 
 extern "C" int aomhip_build_masked_compound_pred_batch(aomhip_ctx *ctx, const aomhip_planes *ref0, int ref0_frame, const aomhip_planes *ref1,
@@ -367,23 +306,12 @@ extern "C" int aomhip_build_masked_compound_pred_batch(aomhip_ctx *ctx, const ao
                                                        int n_blocks, int interp_filter_x, int interp_filter_y, const uint8_t *d_mask,
                                                        const uint32_t *d_mask_offset, int mask_stride, int mask_subw, int mask_subh,
                                                        int subsampling_x, int subsampling_y) {
-  if (!ctx || !ref0 || !ref1 || !pred || !ref0->base || !ref1->base || !pred->base || (n_blocks > 0 && (!d_blocks || !d_mv0 || !d_mv1)) ||
-      n_blocks < 0 || ref0_frame < 0 || ref0_frame >= ref0->n_frames || ref1_frame < 0 || ref1_frame >= ref1->n_frames || pred_frame < 0 ||
-      pred_frame >= pred->n_frames || !valid_block(bw, bh) || ref0->bit_depth != pred->bit_depth || ref1->bit_depth != pred->bit_depth ||
-      ref0->width != ref1->width || ref0->height != ref1->height || interp_filter_x < 0 || interp_filter_x > 3 || interp_filter_y < 0 ||
-      interp_filter_y > 3 || subsampling_x < 0 || subsampling_x > 1 || subsampling_y < 0 || subsampling_y > 1 || !d_mask || mask_stride <= 0 ||
-      mask_subw < 0 || mask_subw > 1 || mask_subh < 0 || mask_subh > 1 || ref0->border < 8 || ref1->border < 8) {
-    set_error("aomhip_build_masked_compound_pred_batch: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (n_blocks == 0) return AOMHIP_OK;
-  if (pred->bit_depth == 8)
-    return launch_compound_pred<uint8_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                         interp_filter_x, interp_filter_y, 0, 0, subsampling_x, subsampling_y, d_mask, d_mask_offset, mask_stride,
-                                         mask_subw, mask_subh);
-  return launch_compound_pred<uint16_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                        interp_filter_x, interp_filter_y, 0, 0, subsampling_x, subsampling_y, d_mask, d_mask_offset, mask_stride,
-                                        mask_subw, mask_subh);
+  const CompoundCall c{ ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks, interp_filter_x, interp_filter_y };
+  if (!c.ok() || !subsampling_ok(subsampling_x, subsampling_y) || !d_mask || mask_stride <= 0 || !subsampling_ok(mask_subw, mask_subh))
+    return invalid("aomhip_build_masked_compound_pred_batch");
+  CompoundBlend b;
+  b.mask = d_mask, b.mask_offset = d_mask_offset, b.mask_stride = mask_stride, b.subw = mask_subw, b.subh = mask_subh;
+  return launch_compound_pred(c, subsampling_x, subsampling_y, b);
 }
 
 extern "C" int aomhip_build_diffwtd_compound_pred_batch(aomhip_ctx *ctx, const aomhip_planes *ref0, int ref0_frame, const aomhip_planes *ref1,
@@ -391,66 +319,40 @@ extern "C" int aomhip_build_diffwtd_compound_pred_batch(aomhip_ctx *ctx, const a
                                                         const aomhip_search_block *d_blocks, const int16_t *d_mv0, const int16_t *d_mv1,
                                                         int n_blocks, int interp_filter_x, int interp_filter_y, int mask_type,
                                                         uint8_t *d_mask_out) {
-  if (!ctx || !ref0 || !ref1 || !pred || !ref0->base || !ref1->base || !pred->base || (n_blocks > 0 && (!d_blocks || !d_mv0 || !d_mv1)) ||
-      n_blocks < 0 || ref0_frame < 0 || ref0_frame >= ref0->n_frames || ref1_frame < 0 || ref1_frame >= ref1->n_frames || pred_frame < 0 ||
-      pred_frame >= pred->n_frames || !valid_block(bw, bh) || ref0->bit_depth != pred->bit_depth || ref1->bit_depth != pred->bit_depth ||
-      ref0->width != ref1->width || ref0->height != ref1->height || interp_filter_x < 0 || interp_filter_x > 3 || interp_filter_y < 0 ||
-      interp_filter_y > 3 || mask_type < 0 || mask_type > 1 || ref0->border < 8 || ref1->border < 8) {
-    set_error("aomhip_build_diffwtd_compound_pred_batch: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (n_blocks == 0) return AOMHIP_OK;
-  if (pred->bit_depth == 8)
-    return launch_compound_pred<uint8_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                         interp_filter_x, interp_filter_y, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0, mask_type + 1, d_mask_out);
-  return launch_compound_pred<uint16_t>(ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks,
-                                        interp_filter_x, interp_filter_y, 0, 0, 0, 0, nullptr, nullptr, 0, 0, 0, mask_type + 1, d_mask_out);
+  const CompoundCall c{ ctx, ref0, ref0_frame, ref1, ref1_frame, pred, pred_frame, bw, bh, d_blocks, d_mv0, d_mv1, n_blocks, interp_filter_x, interp_filter_y };
+  if (!c.ok() || mask_type < 0 || mask_type > 1) return invalid("aomhip_build_diffwtd_compound_pred_batch");
+  CompoundBlend b;
+  b.diffwtd = mask_type + 1, b.mask_out = d_mask_out;
+  return launch_compound_pred(c, 0, 0, b);
 }
 
 extern "C" int aomhip_blend_a64_1d_batch(aomhip_ctx *ctx, const aomhip_planes *pred, int pred_frame, const aomhip_planes *adjacent,
                                          int adjacent_frame, const aomhip_blend_item *d_items, int n_items, const uint8_t *d_masks) {
-  if (!ctx || !pred || !adjacent || !pred->base || !adjacent->base || (n_items > 0 && (!d_items || !d_masks)) || n_items < 0 || pred_frame < 0 ||
-      pred_frame >= pred->n_frames || adjacent_frame < 0 || adjacent_frame >= adjacent->n_frames || pred->bit_depth != adjacent->bit_depth ||
-      pred->width != adjacent->width || pred->height != adjacent->height) {
-    set_error("aomhip_blend_a64_1d_batch: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!ctx || !valid_frame(pred, pred_frame) || !valid_frame(adjacent, adjacent_frame) || (n_items > 0 && (!d_items || !d_masks)) || n_items < 0 ||
+      !same_visible(pred, adjacent))
+    return invalid("aomhip_blend_a64_1d_batch");
   if (n_items == 0) return AOMHIP_OK;
-  const size_t esz = pred->bit_depth == 8 ? 1 : 2;
-  char *d = static_cast<char *>(pred->base) + ((size_t)pred_frame * pred->frame_stride + (size_t)pred->border * pred->stride + pred->border) * esz;
-  const char *s = static_cast<const char *>(adjacent->base) +
-                  ((size_t)adjacent_frame * adjacent->frame_stride + (size_t)adjacent->border * adjacent->stride + adjacent->border) * esz;
-  const dim3 grid((n_items + 3) / 4), block(256);
-  if (esz == 1)
-    hipLaunchKernelGGL(blend_1d_kernel<uint8_t>, grid, block, 0, ctx->stream, reinterpret_cast<uint8_t *>(d), pred->stride,
-                       reinterpret_cast<const uint8_t *>(s), adjacent->stride, d_items, n_items, d_masks);
-  else
-    hipLaunchKernelGGL(blend_1d_kernel<uint16_t>, grid, block, 0, ctx->stream, reinterpret_cast<uint16_t *>(d), pred->stride,
-                       reinterpret_cast<const uint16_t *>(s), adjacent->stride, d_items, n_items, d_masks);
-  AOMHIP_LAUNCH_CHECK();
-  return AOMHIP_OK;
+  return with_pixel(pred->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+    hipLaunchKernelGGL(blend_1d_kernel<T>, dim3((n_items + 3) / 4), dim3(256), 0, ctx->stream, pixels<T>(pred, pred_frame), pred->stride,
+                       pixels<const T>(adjacent, adjacent_frame), adjacent->stride, d_items, n_items, d_masks);
+    AOMHIP_LAUNCH_CHECK();
+    return AOMHIP_OK;
+  });
 }
 
 extern "C" int aomhip_build_pred_fullpel(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame,
                                          const aomhip_planes *pred, int pred_frame, int bw, int bh,
                                          const aomhip_search_block *d_blocks, const int16_t *d_fullpel_mv, int n_blocks) {
-  if (!ctx || !ref || !pred || !ref->base || !pred->base || !d_blocks || !d_fullpel_mv || n_blocks < 0 || ref_frame < 0 ||
-      ref_frame >= ref->n_frames || pred_frame < 0 || pred_frame >= pred->n_frames || !valid_block(bw, bh) ||
-      ref->bit_depth != pred->bit_depth) {
-    set_error("aomhip_build_pred_fullpel: invalid argument");
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!ctx || !valid_frame(ref, ref_frame) || !valid_frame(pred, pred_frame) || !d_blocks || !d_fullpel_mv || n_blocks < 0 || !valid_block(bw, bh) ||
+      ref->bit_depth != pred->bit_depth)
+    return invalid("aomhip_build_pred_fullpel");
   if (n_blocks == 0) return AOMHIP_OK;
-  const size_t esz = pred->bit_depth == 8 ? 1 : 2;
-  char *d = static_cast<char *>(pred->base) +
-            ((size_t)pred_frame * pred->frame_stride + (size_t)pred->border * pred->stride + pred->border) * esz;
-  const dim3 grid((n_blocks + 3) / 4), block(256);
-  if (esz == 1)
-    hipLaunchKernelGGL(pred_copy_kernel<uint8_t>, grid, block, 0, ctx->stream, view_of<uint8_t>(*ref), ref_frame,
-                       reinterpret_cast<uint8_t *>(d), pred->stride, d_blocks, d_fullpel_mv, n_blocks, bw, bh);
-  else
-    hipLaunchKernelGGL(pred_copy_kernel<uint16_t>, grid, block, 0, ctx->stream, view_of<uint16_t>(*ref), ref_frame,
-                       reinterpret_cast<uint16_t *>(d), pred->stride, d_blocks, d_fullpel_mv, n_blocks, bw, bh);
-  AOMHIP_LAUNCH_CHECK();
-  return AOMHIP_OK;
+  return with_pixel(pred->bit_depth, [&](auto px) -> int {
+    using T = decltype(px);
+    hipLaunchKernelGGL(pred_copy_kernel<T>, dim3((n_blocks + 3) / 4), dim3(256), 0, ctx->stream, view_of<T>(*ref), ref_frame,
+                       pixels<T>(pred, pred_frame), pred->stride, d_blocks, d_fullpel_mv, n_blocks, bw, bh);
+    AOMHIP_LAUNCH_CHECK();
+    return AOMHIP_OK;
+  });
 }

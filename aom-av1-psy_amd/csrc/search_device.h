@@ -317,10 +317,7 @@ __device__ __forceinline__ uint32_t wave_variance(const T *ap, int astride, int 
   constexpr int UE = 4;  // pixels per unit
   constexpr int UPR = W / UE;
   constexpr int U = UPR * H;
-  constexpr uint8_t kBil[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 },
-                                   { 64, 64 }, { 48, 80 },  { 32, 96 }, { 16, 112 } };  // aom_filter.h:43-50
-  static_assert(kBil[3][0] == 128 - 16 * 3 && kBil[3][1] == 16 * 3 && kBil[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (yoff & 7) << 4, fy0 = 128 - fy1;   // = kBil[off & 7]: {128 - 16 i, 16 i} (aom_filter.h:43-50) by arithmetic -- indexed as a table the compiler put it in memory: two loads on the chain of every candidate
+  const BilinearPair bfx = bilinear_pair(xoff), bfy = bilinear_pair(yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int64_t sum = 0, sse = 0;
   for (int u = lane; u < U; u += 64) {
     const int row = u / UPR, col = (u % UPR) * UE;
@@ -332,9 +329,9 @@ __device__ __forceinline__ uint32_t wave_variance(const T *ap, int astride, int 
     for (int i = 0; i < UE; ++i) {
       int av;
       if constexpr (SUBPEL) {
-        const int h0 = ((int)a0[i] * fx0 + (int)a0[i + 1] * fx1 + 64) >> 7;
-        const int h1 = ((int)a0[astride + i] * fx0 + (int)a0[astride + i + 1] * fx1 + 64) >> 7;
-        av = (__mul24(h0, fy0) + __mul24(h1, fy1) + 64) >> 7;   // h <= 4095: 24-bit multiplies (v_mul_lo_u32 is quarter rate)
+        const int h0 = ((int)a0[i] * bfx.f0 + (int)a0[i + 1] * bfx.f1 + 64) >> 7;
+        const int h1 = ((int)a0[astride + i] * bfx.f0 + (int)a0[astride + i + 1] * bfx.f1 + 64) >> 7;
+        av = (__mul24(h0, bfy.f0) + __mul24(h1, bfy.f1) + 64) >> 7;   // h <= 4095: 24-bit multiplies (v_mul_lo_u32 is quarter rate)
         av &= (sizeof(T) == 1) ? 0xFF : 0xFFFF;
       } else {
         av = a0[i];
@@ -508,10 +505,7 @@ __device__ __forceinline__ uint32_t group16_variance(const T *ap, int astride, i
   constexpr int U = UPR * H;
   constexpr int UB = UE * (int)sizeof(T);
   using L = typename MLoad<UB>::type;
-  constexpr uint8_t kBil[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 },
-                                   { 64, 64 }, { 48, 80 },  { 32, 96 }, { 16, 112 } };  // aom_filter.h:43-50
-  static_assert(kBil[3][0] == 128 - 16 * 3 && kBil[3][1] == 16 * 3 && kBil[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (yoff & 7) << 4, fy0 = 128 - fy1;   // = kBil[off & 7]: {128 - 16 i, 16 i} (aom_filter.h:43-50) by arithmetic -- indexed as a table the compiler put it in memory: two loads on the chain of every candidate
+  const BilinearPair bfx = bilinear_pair(xoff), bfy = bilinear_pair(yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int32_t sum = 0;   // |Σd| <= 4095 * W * H < 2^31 for every block size
   uint64_t sse = 0;
   if (active) {
@@ -530,9 +524,9 @@ __device__ __forceinline__ uint32_t group16_variance(const T *ap, int astride, i
         for (int i = 0; i < UE; ++i) {
           const int p00 = px_of<T>(r0.v, i), p01 = i + 1 < UE ? px_of<T>(r0.v, i + 1 < UE ? i + 1 : i) : e0;
           const int p10 = px_of<T>(r1.v, i), p11 = i + 1 < UE ? px_of<T>(r1.v, i + 1 < UE ? i + 1 : i) : e1;
-          const int h0 = (__mul24(p00, fx0) + __mul24(p01, fx1) + 64) >> 7;
-          const int h1 = (__mul24(p10, fx0) + __mul24(p11, fx1) + 64) >> 7;
-          int av = (__mul24(h0, fy0) + __mul24(h1, fy1) + 64) >> 7;   // h <= 4095: 24-bit multiplies (v_mul_lo_u32 is quarter rate)
+          const int h0 = (__mul24(p00, bfx.f0) + __mul24(p01, bfx.f1) + 64) >> 7;
+          const int h1 = (__mul24(p10, bfx.f0) + __mul24(p11, bfx.f1) + 64) >> 7;
+          int av = (__mul24(h0, bfy.f0) + __mul24(h1, bfy.f1) + 64) >> 7;   // h <= 4095: 24-bit multiplies (v_mul_lo_u32 is quarter rate)
           av &= (sizeof(T) == 1) ? 0xFF : 0xFFFF;
           avv[i] = av;
         }

@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "pred_device.h"
 #include "search_device.h"
 
 #ifndef AOMHIP_SUBPEL_WAVES
@@ -26,30 +27,8 @@ namespace aomhip {
 // phase 2 * (mv & 7): each pass rounds by FILTER_BITS = 7 and clips to the pixel range; then vfp->vf(pred, w, src).
 // Phase 0 is {0,0,0,128,0,0,0,0}, the identity, so the reference's "skip the pass when the offset is 0" needs no
 // special case; taps 0 and 7 are zero in every phase, so six taps (offsets -2 .. +3) give the same sums.
-__device__ constexpr int16_t kSubPel8[16][8] = {  // av1_sub_pel_filters_8 (AV1 spec; av1/common/filter.h:124-141)
-  { 0, 0, 0, 128, 0, 0, 0, 0 },      { 0, 2, -6, 126, 8, -2, 0, 0 },    { 0, 2, -10, 122, 18, -4, 0, 0 },
-  { 0, 2, -12, 116, 28, -8, 2, 0 },  { 0, 2, -14, 110, 38, -10, 2, 0 }, { 0, 2, -14, 102, 48, -12, 2, 0 },
-  { 0, 2, -16, 94, 58, -12, 2, 0 },  { 0, 2, -14, 84, 66, -12, 2, 0 },  { 0, 2, -14, 76, 76, -14, 2, 0 },
-  { 0, 2, -12, 66, 84, -14, 2, 0 },  { 0, 2, -12, 58, 94, -16, 2, 0 },  { 0, 2, -12, 48, 102, -14, 2, 0 },
-  { 0, 2, -10, 38, 110, -14, 2, 0 }, { 0, 2, -8, 28, 116, -12, 2, 0 },  { 0, 0, -4, 18, 122, -10, 2, 0 },
-  { 0, 0, -2, 8, 126, -6, 2, 0 }
-};
-
-// av1_get_filter(subpel_search_type) (av1/common/filter.h:270-279): USE_4_TAPS is av1_interp_4tap[EIGHTTAP_REGULAR] = av1_sub_pel_filters_4
-// (:205-215; speed 1 - 2 of the good-quality presets, speed_features.c:957), USE_2_TAPS av1_interp_4tap[BILINEAR] = av1_bilinear_filters
-// (:111-121; { 128 - 8 p, 8 p } at taps 3 and 4) -- all stored as 8 taps, all zero at taps 0 and 7, all with the identity at phase 0.
-__device__ constexpr int16_t kSubPel4[16][8] = {
-  { 0, 0, 0, 128, 0, 0, 0, 0 },     { 0, 0, -4, 126, 8, -2, 0, 0 },   { 0, 0, -8, 122, 18, -4, 0, 0 },  { 0, 0, -10, 116, 28, -6, 0, 0 },
-  { 0, 0, -12, 110, 38, -8, 0, 0 }, { 0, 0, -12, 102, 48, -10, 0, 0 }, { 0, 0, -14, 94, 58, -10, 0, 0 }, { 0, 0, -12, 84, 66, -10, 0, 0 },
-  { 0, 0, -12, 76, 76, -12, 0, 0 }, { 0, 0, -10, 66, 84, -12, 0, 0 }, { 0, 0, -10, 58, 94, -14, 0, 0 }, { 0, 0, -10, 48, 102, -12, 0, 0 },
-  { 0, 0, -8, 38, 110, -12, 0, 0 }, { 0, 0, -6, 28, 116, -10, 0, 0 }, { 0, 0, -4, 18, 122, -8, 0, 0 },  { 0, 0, -2, 8, 126, -4, 0, 0 }
-};
-// tap k + 1 (k = 0 .. 5) of the kernel of 1/8-pel offset `off` under SUBPEL_SEARCH_TYPE `type`
-__device__ __forceinline__ int up_tap(int type, int off, int k) {
-  const int ph = 2 * (off & 7);
-  if (type == 1) return k == 2 ? 128 - 8 * ph : (k == 3 ? 8 * ph : 0);
-  return type == 2 ? kSubPel4[ph][k + 1] : kSubPel8[ph][k + 1];
-}
+// av1_get_filter(subpel_search_type) (av1/common/filter.h:270-279) picks the kernel: USE_4_TAPS is av1_sub_pel_filters_4 (speed 1 - 2 of the good-quality
+// presets, speed_features.c:957), USE_2_TAPS av1_bilinear_filters -- all with the identity at phase 0.  The taps are up_tap() of pred_device.h.
 
 // The up-sampling taps of one SUBPEL_SEARCH_TYPE as an LDS table: 8 phases x kUpTapDwords packed pairs (see group16_upsampled_variance)
 constexpr int kUpTapDwords = 5;
@@ -57,7 +36,7 @@ __device__ __forceinline__ void fill_up_tap_table(uint32_t *tbl, int type, int t
   if (tid < 8 * kUpTapDwords) {
     const int ph = tid / kUpTapDwords, e = tid - ph * kUpTapDwords;
     const int k0 = e < 3 ? 2 * e : 2 * (e - 3) + 1;   // pairs (0,1) (2,3) (4,5) | (1,2) (3,4)
-    tbl[tid] = (uint32_t)(uint16_t)(int16_t)up_tap(type, ph, k0) | ((uint32_t)(uint16_t)(int16_t)up_tap(type, ph, k0 + 1) << 16);
+    tbl[tid] = (uint32_t)(uint16_t)(int16_t)up_tap(type, 2 * ph, k0) | ((uint32_t)(uint16_t)(int16_t)up_tap(type, 2 * ph, k0 + 1) << 16);
   }
 }
 
@@ -98,7 +77,7 @@ __device__ __forceinline__ uint32_t group16_upsampled_variance(const T *ap, int 
   [[maybe_unused]] const unsigned long long ups_t0 = UPS_T();
   const int pmax = sizeof(T) == 1 ? 255 : (1 << bit_depth) - 1;
   // The six taps of both offsets as packed pairs out of the kernel's LDS table (kUpTapDwords per phase: pairs (0,1) (2,3) (4,5), then (1,2) (3,4) for the narrow
-  // kernels).  Looked up with up_tap() here -- kSubPel4 / kSubPel8 indexed by a lane group's offset: twelve loads from constant memory -- they were a memory round
+  // kernels).  Looked up with up_tap() here -- the table indexed by a lane group's offset: twelve loads from constant memory -- they were a memory round
   // trip at the head of every call: 2 200 of a call's 8 900 clocks at 16x16 (phase clocks of an AOMHIP_UPS_PROF build, profiles/r06_subpel_8tap.md).
   typedef short s16x2_t __attribute__((ext_vector_type(2)));
   s16x2_t kxp[3], kyp[3], kxq[2], kyq[2];   // tap pairs for v_dot2_i32_i16
@@ -322,21 +301,18 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
   constexpr int SZ = (int)sizeof(T);
   constexpr int UE = W >= 8 ? 8 : 4;
   constexpr int K = ((UE + 1) * SZ + 3) / 4;  // dwords holding UE + 1 pixels
-  constexpr uint8_t kBil[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 },
-                                   { 64, 64 }, { 48, 80 },  { 32, 96 }, { 16, 112 } };  // aom_filter.h:43-50
-  static_assert(kBil[3][0] == 128 - 16 * 3 && kBil[3][1] == 16 * 3 && kBil[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (yoff & 7) << 4, fy0 = 128 - fy1;   // = kBil[off & 7]: {128 - 16 i, 16 i} (aom_filter.h:43-50) by arithmetic -- indexed as a table the compiler put it in memory: two loads on the chain of every candidate
+  const BilinearPair bfx = bilinear_pair(xoff), bfy = bilinear_pair(yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int32_t sum = 0;
   uint64_t sse = 0;
   using FU = FootUnits<T, W, H, NSRC>;
   typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
   typedef short s16x2_t __attribute__((ext_vector_type(2)));
   // ---- 8-bit planes.  Pixels sit four to a dword: a horizontal tap pair is ONE v_dot4_u32_u8 of the window realigned to the pixel (v_alignbit, free
-  // at every fourth) with the filter bytes (fx0, fx1, 0, 0) and the rounding constant as its accumulator; two results pack into 16-bit halves
+  // at every fourth) with the filter bytes (f0, f1, 0, 0) and the rounding constant as its accumulator; two results pack into 16-bit halves
   // (<= 255 * 128 + 64) and everything after is packed 16-bit arithmetic -- one shift, the vertical pass as v_pk_mul / v_pk_mad / shift, the
   // difference from the source pair (one v_perm_b32 out of its dword) through v_pk_sub_i16 and two v_dot2_i32_i16.  The per-pixel field extractions and
   // 24-bit multiplies this replaces made the 8-bit kernel SLOWER than the 16-bit one (inner loop, 4K: 146 against 102 us, tools/bd_audit.sh).
-  [[maybe_unused]] const uint32_t fxq = (uint32_t)fx0 | ((uint32_t)fx1 << 8);
+  [[maybe_unused]] const uint32_t fxq = (uint32_t)bfx.f0 | ((uint32_t)bfx.f1 << 8);
   [[maybe_unused]] auto hrow8 = [&](const uint32_t *p, unsigned sh, uint32_t (&hp)[UE / 2]) {
     uint32_t d[K + 1], w[K];
 #pragma unroll
@@ -355,8 +331,8 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
   [[maybe_unused]] auto pair8 = [](uint32_t dw, int pi) -> s16x2_t {   // pixels (2 pi, 2 pi + 1) of a dword of four as 16-bit halves
     return __builtin_bit_cast(s16x2_t, __builtin_amdgcn_perm(0u, dw, (pi & 1) ? 0x0c030c02u : 0x0c010c00u));
   };
-  [[maybe_unused]] auto vpass8 = [&](uint32_t h0, uint32_t h1) -> s16x2_t {   // (h0 * fy0 + h1 * fy1 + 64) >> 7 on both halves
-    const u16x2_t f0 = { (unsigned short)fy0, (unsigned short)fy0 }, f1 = { (unsigned short)fy1, (unsigned short)fy1 }, r = { 64, 64 };
+  [[maybe_unused]] auto vpass8 = [&](uint32_t h0, uint32_t h1) -> s16x2_t {   // (h0 * bfy.f0 + h1 * bfy.f1 + 64) >> 7 on both halves
+    const u16x2_t f0 = { (unsigned short)bfy.f0, (unsigned short)bfy.f0 }, f1 = { (unsigned short)bfy.f1, (unsigned short)bfy.f1 }, r = { 64, 64 };
     return __builtin_bit_cast(s16x2_t, (__builtin_bit_cast(u16x2_t, h0) * f0 + __builtin_bit_cast(u16x2_t, h1) * f1 + r) >> (unsigned short)7);
   };
   if constexpr (FU::STACKED && SZ == 1) {
@@ -400,7 +376,7 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
     }
   } else if constexpr (FU::STACKED) {
     if (active) {
-      const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)fx0 | ((uint32_t)fx1 << 16));
+      const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)bfx.f0 | ((uint32_t)bfx.f1 << 16));
       const s16x2_t ones = { 1, 1 };
       const int row0 = FU::row(j, 0), col = FU::col(j, 0);
       const int xb = (x + col) * SZ;
@@ -445,8 +421,8 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
       for (int k = 0; k < NSRC; ++k) {
 #pragma unroll
         for (int i = 0; i < UE; i += 2) {
-          const int a0 = (__mul24(hh[k][i], fy0) + __mul24(hh[k + 1][i], fy1) + 64) >> 7;
-          const int a1 = (__mul24(hh[k][i + 1], fy0) + __mul24(hh[k + 1][i + 1], fy1) + 64) >> 7;
+          const int a0 = (__mul24(hh[k][i], bfy.f0) + __mul24(hh[k + 1][i], bfy.f1) + 64) >> 7;
+          const int a1 = (__mul24(hh[k][i + 1], bfy.f0) + __mul24(hh[k + 1][i + 1], bfy.f1) + 64) >> 7;
           const s16x2_t pv = __builtin_bit_cast(s16x2_t, (uint32_t)a0 | ((uint32_t)a1 << 16));
           const s16x2_t d = pv - __builtin_bit_cast(s16x2_t, srcu[k].v[i >> 1]);
           us = __builtin_amdgcn_sdot2(d, ones, us, false);
@@ -482,7 +458,7 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
           // (sum and sum of squares).  The kernel is bound by VALU issue (profiles/r02_search_bound.md): 18 -> 11 instructions per pixel.
           typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
           typedef short s16x2_t __attribute__((ext_vector_type(2)));
-          const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)fx0 | ((uint32_t)fx1 << 16));
+          const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)bfx.f0 | ((uint32_t)bfx.f1 << 16));
           const s16x2_t ones = { 1, 1 };
           int av[UE];
 #pragma unroll
@@ -491,7 +467,7 @@ __device__ __forceinline__ uint32_t group16_variance_foot(const uint32_t *foot, 
             const uint32_t q1 = (i & 1) ? __builtin_amdgcn_alignbit(w1[(i + 1) >> 1], w1[i >> 1], 16) : w1[i >> 1];
             const int h0 = (int)(__builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, q0), fxp, 64u, false) >> 7);
             const int h1 = (int)(__builtin_amdgcn_udot2(__builtin_bit_cast(u16x2_t, q1), fxp, 64u, false) >> 7);
-            av[i] = (__mul24(h0, fy0) + __mul24(h1, fy1) + 64) >> 7;   // <= the pixel maximum: the reference's uint16_t store changes nothing
+            av[i] = (__mul24(h0, bfy.f0) + __mul24(h1, bfy.f1) + 64) >> 7;   // <= the pixel maximum: the reference's uint16_t store changes nothing
           }
 #pragma unroll
           for (int i = 0; i < UE; i += 2) {
@@ -537,13 +513,11 @@ __device__ __forceinline__ uint32_t wave_variance_foot(const uint32_t *foot, int
   constexpr int UE = 8, UPR = W / UE, K = 5;
   typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
   typedef short s16x2_t __attribute__((ext_vector_type(2)));
-  constexpr uint8_t kBil[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 }, { 64, 64 }, { 48, 80 }, { 32, 96 }, { 16, 112 } };
-  static_assert(kBil[3][0] == 128 - 16 * 3 && kBil[3][1] == 16 * 3 && kBil[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (yoff & 7) << 4, fy0 = 128 - fy1;   // = kBil[off & 7]: {128 - 16 i, 16 i} (aom_filter.h:43-50) by arithmetic -- indexed as a table the compiler put it in memory: two loads on the chain of every candidate
+  const BilinearPair bfx = bilinear_pair(xoff), bfy = bilinear_pair(yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int us = 0;
   uint32_t uq = 0;
   if (active && lane < 32) {
-    const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)fx0 | ((uint32_t)fx1 << 16));
+    const u16x2_t fxp = __builtin_bit_cast(u16x2_t, (uint32_t)bfx.f0 | ((uint32_t)bfx.f1 << 16));
     const s16x2_t ones = { 1, 1 };
     const int row = lane / UPR, col = (lane % UPR) * UE;
     const int xb = (x + col) * 2;
@@ -565,8 +539,8 @@ __device__ __forceinline__ uint32_t wave_variance_foot(const uint32_t *foot, int
     }
 #pragma unroll
     for (int i = 0; i < UE; i += 2) {
-      const int a0 = (__mul24(hh[0][i], fy0) + __mul24(hh[1][i], fy1) + 64) >> 7;
-      const int a1 = (__mul24(hh[0][i + 1], fy0) + __mul24(hh[1][i + 1], fy1) + 64) >> 7;
+      const int a0 = (__mul24(hh[0][i], bfy.f0) + __mul24(hh[1][i], bfy.f1) + 64) >> 7;
+      const int a1 = (__mul24(hh[0][i + 1], bfy.f0) + __mul24(hh[1][i + 1], bfy.f1) + 64) >> 7;
       const s16x2_t pv = __builtin_bit_cast(s16x2_t, (uint32_t)a0 | ((uint32_t)a1 << 16));
       const s16x2_t d = pv - __builtin_bit_cast(s16x2_t, srcw[i >> 1]);
       us = __builtin_amdgcn_sdot2(d, ones, us, false);

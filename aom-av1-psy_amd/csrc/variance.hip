@@ -37,8 +37,7 @@ __global__ __launch_bounds__(kVarThreads) void variance_kernel(PlaneView<T> src,
   const int64_t fo = (int64_t)(first_frame + f_rel);
   const T *sp = src.origin + fo * src.frame_stride + (int64_t)c.sy * src.stride + c.sx;
   const T *rp = ref.origin + fo * ref.frame_stride + (int64_t)c.ry * ref.stride + c.rx;
-  static_assert(kBilinear[3][0] == 128 - 16 * 3 && kBilinear[3][1] == 16 * 3 && kBilinear[7][0] == 16, "bilinear taps are 128 - 16 i, 16 i");
-  const int fx1 = (c.xoff & 7) << 4, fx0 = 128 - fx1, fy1 = (c.yoff & 7) << 4, fy0 = 128 - fy1;   // (by arithmetic: a table index is a memory load)
+  const BilinearPair bfx = bilinear_pair(c.xoff), bfy = bilinear_pair(c.yoff);   // by arithmetic: a table index is a memory load on every candidate's chain
   int64_t sum = 0;
   uint64_t sse = 0;
 #pragma unroll
@@ -60,9 +59,9 @@ __global__ __launch_bounds__(kVarThreads) void variance_kernel(PlaneView<T> src,
       load_elems<T, E>(a1 + 1, r1n);
 #pragma unroll
       for (int i = 0; i < E; ++i) {
-        const int h0 = (r0[i] * fx0 + r0n[i] * fx1 + 64) >> 7;  // first pass, uint16 range
-        const int h1 = (r1[i] * fx0 + r1n[i] * fx1 + 64) >> 7;
-        apx[i] = (__mul24(h0, fy0) + __mul24(h1, fy1) + 64) >> 7;               // second pass
+        const int h0 = (r0[i] * bfx.f0 + r0n[i] * bfx.f1 + 64) >> 7;  // first pass, uint16 range
+        const int h1 = (r1[i] * bfx.f0 + r1n[i] * bfx.f1 + 64) >> 7;
+        apx[i] = (__mul24(h0, bfy.f0) + __mul24(h1, bfy.f1) + 64) >> 7;               // second pass
         if constexpr (sizeof(T) == 1) apx[i] &= 0xFF;           // stored to uint8_t temp2 (variance.c:155)
         else apx[i] &= 0xFFFF;
       }

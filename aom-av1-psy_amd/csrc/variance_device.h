@@ -17,9 +17,6 @@ template <> struct VLoad<16> { using type = VU128; };
 template <> struct VLoad<8> { using type = VU64; };
 template <> struct VLoad<4> { using type = VU32; };
 
-__device__ constexpr uint8_t kBilinear[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 },
-                                                 { 64, 64 }, { 48, 80 },  { 32, 96 }, { 16, 112 } };
-
 template <int TPC> __device__ __forceinline__ int32_t gsum32(int32_t v) {
   if constexpr (TPC >= 2) v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false);
   if constexpr (TPC >= 4) v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false);

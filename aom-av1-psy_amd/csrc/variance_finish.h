@@ -7,6 +7,19 @@
 
 namespace aomhip {
 
+// bilinear_filters_2t (aom_dsp/aom_filter.h:43-50) and the pair of an eighth-pel offset by arithmetic, which is what the kernels use: indexed as a
+// table the compiler puts it in memory
+__device__ constexpr uint8_t kBilinear[8][2] = { { 128, 0 }, { 112, 16 }, { 96, 32 }, { 80, 48 }, { 64, 64 }, { 48, 80 }, { 32, 96 }, { 16, 112 } };
+struct BilinearPair { int f0, f1; };
+__host__ __device__ constexpr BilinearPair bilinear_pair(int off8) {
+  const int f1 = (off8 & 7) << 4;
+  return { 128 - f1, f1 };
+}
+constexpr bool bilinear_pair_is_the_table(int i = 0) {
+  return i == 8 || (bilinear_pair(i).f0 == kBilinear[i][0] && bilinear_pair(i).f1 == kBilinear[i][1] && bilinear_pair_is_the_table(i + 1));
+}
+static_assert(bilinear_pair_is_the_table(), "bilinear taps are 128 - 16 i, 16 i");
+
 // var and sse of a block of 2^log2n pixels from the sum and the sum of squares of its differences: sse rounded by 4 / 8 bits and the sum by 2 / 4
 // bits at 10 / 12 bits, sum^2 >> log2n, the difference unsigned at 8 bits and clamped at 0 otherwise
 __device__ __forceinline__ void finish(int64_t sum64, uint64_t sse64, int bit_depth, int log2n, uint32_t *var, uint32_t *sse) {

@@ -13,6 +13,7 @@
 // CONV_BUF (uint16, addressed like the plane); MODE 2 = the second reference blended with it -- (a + b) >> 1 or the distance weights
 // (a fwd + b bck) >> DIST_PRECISION_BITS -- offsets removed, rounded by round_bits, clipped into the prediction.
 #include "common.h"
+#include "pred_device.h"
 
 namespace aomhip {
 namespace {
@@ -21,12 +22,6 @@ __device__ const int16_t kWarpedFilter[193][8] __attribute__((aligned(16))) = {
 #include "warp_table.inc"
 };
 #include "warp_error_table.inc"
-
-struct WarpCompound {
-  uint16_t *conv;      // CONV_BUF: element (row, col) of the plane at conv[row * conv_stride + col]
-  int conv_stride;
-  int use_dist_wtd, fwd_offset, bck_offset;
-};
 
 // One 8 x 8 tile at (i, j) of a block (p_col, p_row, p_width, p_height) through the model: both passes, returning this lane's vertical sum rounded by
 // reduce_bits_vert (offsets still in) and whether the lane's pixel (i + k + 4, j + l + 4), k = lane / 8 - 4, l = lane % 8 - 4, lies inside the block.
@@ -38,11 +33,8 @@ struct WarpModel {
 template <typename T>
 __device__ __forceinline__ bool warp_tile(const T *__restrict__ rp, int ref_stride, int width, int height, const WarpModel &m, int ssx, int ssy, int bd, bool compound,
                                           int i, int j, int p_col, int p_row, int p_width, int p_height, int32_t *tmp, int lane, int32_t *out) {
-  const bool hbd = sizeof(T) == 2;
-  const int round_0 = bd == 12 ? 5 : 3;   // ROUND0_BITS (+ 2 at 12 bits): get_conv_params_no_round (av1/common/convolve.h)
-  const int extra = hbd ? max(bd + 7 - round_0 - 14, 0) : 0;
-  const int reduce_bits_horiz = round_0 + extra, reduce_bits_vert = compound ? 7 : 14 - reduce_bits_horiz;   // COMPOUND_ROUND1_BITS
-  const int offset_bits_horiz = bd + 6, offset_bits_vert = bd + 14 - reduce_bits_horiz;
+  // reduce_bits_horiz / _vert are round_0 / round_1: the high-bit-depth form's extra bits, max(bd + 7 - round_0 - 14, 0), are 0 at 10 and at 12 bits
+  const ConvParams cp = conv_params(bd, compound);
   // the centre of the tile in luma coordinates, through the model, back to this plane's coordinates
   const int32_t src_x = (j + 4) << ssx, src_y = (i + 4) << ssy;
   const int64_t dst_x = (int64_t)m.mat[2] * src_x + (int64_t)m.mat[3] * src_y + (int64_t)m.mat[0];
@@ -64,10 +56,10 @@ __device__ __forceinline__ bool warp_tile(const T *__restrict__ rp, int ref_stri
                        (int)(int16_t)(cw.z & 0xffff), cw.z >> 16, (int)(int16_t)(cw.w & 0xffff), cw.w >> 16 };
     const int ix = ix4 + l - 3;
     const T *row = rp + (int64_t)iy * ref_stride;
-    int32_t sum = 1 << offset_bits_horiz;
+    int32_t sum = cp.hoff;
 #pragma unroll
     for (int q = 0; q < 8; ++q) sum += (int)row[min(max(ix + q, 0), width - 1)] * c[q];
-    tmp[t] = (sum + ((1 << reduce_bits_horiz) >> 1)) >> reduce_bits_horiz;
+    tmp[t] = sum >> cp.round_0;
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -82,10 +74,10 @@ __device__ __forceinline__ bool warp_tile(const T *__restrict__ rp, int ref_stri
     const int4 cw = *reinterpret_cast<const int4 *>(kWarpedFilter[offs]);
     const int c[8] = { (int)(int16_t)(cw.x & 0xffff), cw.x >> 16, (int)(int16_t)(cw.y & 0xffff), cw.y >> 16,
                        (int)(int16_t)(cw.z & 0xffff), cw.z >> 16, (int)(int16_t)(cw.w & 0xffff), cw.w >> 16 };
-    int32_t sum = 1 << offset_bits_vert;
+    int32_t sum = cp.voff;
 #pragma unroll
     for (int q = 0; q < 8; ++q) sum += tmp[(k + q + 4) * 8 + (l + 4)] * c[q];
-    *out = (sum + ((1 << reduce_bits_vert) >> 1)) >> reduce_bits_vert;
+    *out = sum >> cp.round_1;
   }
   return inside;
 }
@@ -93,7 +85,7 @@ __device__ __forceinline__ bool warp_tile(const T *__restrict__ rp, int ref_stri
 template <typename T, int MODE>
 __global__ __launch_bounds__(256) void warp_affine_kernel(PlaneView<T> ref, int ref_frame, int width, int height, T *__restrict__ pred_origin, int64_t pred_frame_off,
                                                           int pred_stride, int ssx, int ssy, int bd, const aomhip_warp_block *__restrict__ blocks, int n_blocks,
-                                                          WarpCompound cm) {
+                                                          ConvBuf cm) {
   __shared__ int32_t tmp_all[4][15 * 8];
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
   const int bi = blockIdx.x;
@@ -110,8 +102,7 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(PlaneView<T> ref, int 
   for (int k = 0; k < 6; ++k) m.mat[k] = __builtin_amdgcn_readfirstlane(b.mat[k]);
   m.alpha = __builtin_amdgcn_readfirstlane((int)b.alpha), m.beta = __builtin_amdgcn_readfirstlane((int)b.beta);
   m.gamma = __builtin_amdgcn_readfirstlane((int)b.gamma), m.delta = __builtin_amdgcn_readfirstlane((int)b.delta);
-  const int round_0 = bd == 12 ? 5 : 3, round_1 = MODE ? 7 : 14 - round_0;
-  [[maybe_unused]] const int round_bits = 14 - round_0 - round_1, offset_bits = bd + 14 - round_0;
+  const ConvParams cp = conv_params(bd, MODE != 0);
   int32_t sum;
   if (!warp_tile<T>(ref.origin + (int64_t)ref_frame * ref.frame_stride, ref.stride, width, height, m, ssx, ssy, bd, MODE != 0, i, j, p_col, p_row, p_width, p_height,
                     tmp_all[wave], lane, &sum))
@@ -120,16 +111,9 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(PlaneView<T> ref, int 
   if constexpr (MODE == 1) {
     cm.conv[(int64_t)(i + k + 4) * cm.conv_stride + (j + l + 4)] = (uint16_t)sum;   // CONV_BUF_TYPE
   } else {
-    int v;
-    if constexpr (MODE == 2) {
-      int t32 = (int)cm.conv[(int64_t)(i + k + 4) * cm.conv_stride + (j + l + 4)];
-      t32 = cm.use_dist_wtd ? (t32 * cm.fwd_offset + sum * cm.bck_offset) >> 4 : (t32 + sum) >> 1;   // DIST_PRECISION_BITS
-      t32 = t32 - (1 << (offset_bits - round_1)) - (1 << (offset_bits - round_1 - 1));
-      v = (t32 + ((1 << round_bits) >> 1)) >> round_bits;
-    } else {
-      v = sum - (1 << (bd - 1)) - (1 << bd);
-    }
-    pred_origin[pred_frame_off + (int64_t)(i + k + 4) * pred_stride + (j + l + 4)] = (T)min(max(v, 0), (1 << bd) - 1);
+    const int v = MODE == 2 ? compound_finish((int)cm.conv[(int64_t)(i + k + 4) * cm.conv_stride + (j + l + 4)], sum, cm.use_dist_wtd, cm.fwd_offset, cm.bck_offset, cp)
+                            : conv_to_pixel(sum, cp);   // (a single prediction: round_bits is 0)
+    pred_origin[pred_frame_off + (int64_t)(i + k + 4) * pred_stride + (j + l + 4)] = (T)v;
   }
 }
 
@@ -213,7 +197,7 @@ __global__ __launch_bounds__(256) void warp_error_sum_kernel(const int32_t *__re
 using namespace aomhip;
 
 static int warp_launch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred, int pred_frame, int subsampling_x, int subsampling_y,
-                       const aomhip_warp_block *d_blocks, int n_blocks, int max_block_width, int max_block_height, int mode, WarpCompound cm, const char *who) {
+                       const aomhip_warp_block *d_blocks, int n_blocks, int max_block_width, int max_block_height, int mode, ConvBuf cm, const char *who) {
   if (!ctx || !ref || !ref->base || n_blocks < 0 || (n_blocks > 0 && !d_blocks) || ref_frame < 0 || ref_frame >= ref->n_frames ||
       (mode != 1 && (!pred || !pred->base || pred_frame < 0 || pred_frame >= pred->n_frames || (ref->bit_depth == 8) != (pred->bit_depth == 8))) ||
       (subsampling_x | subsampling_y) < 0 || subsampling_x > 1 || subsampling_y > 1 || max_block_width < 1 || max_block_height < 1 || max_block_width > 128 ||
@@ -225,7 +209,7 @@ static int warp_launch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame,
   AOMHIP_TRY(hipSetDevice(ctx->device));
   const int tiles = ((max_block_width + 7) / 8) * ((max_block_height + 7) / 8);
   const dim3 grid((unsigned)n_blocks, (unsigned)((tiles + 3) / 4)), block(256);
-  const int64_t poff = pred ? (int64_t)pred_frame * pred->frame_stride + (int64_t)pred->border * pred->stride + pred->border : 0;
+  const int64_t poff = pred ? frame_origin(pred, pred_frame) : 0;
   void *pbase = pred ? pred->base : nullptr;
   const int pstride = pred ? pred->stride : 0;
 #define LAUNCH(T, M)                                                                                                                                   \
@@ -244,7 +228,7 @@ static int warp_launch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame,
 extern "C" int aomhip_warp_affine_batch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred, int pred_frame, int subsampling_x,
                                         int subsampling_y, const aomhip_warp_block *d_blocks, int n_blocks, int max_block_width, int max_block_height) {
   return warp_launch(ctx, ref, ref_frame, pred, pred_frame, subsampling_x, subsampling_y, d_blocks, n_blocks, max_block_width, max_block_height, 0,
-                     WarpCompound{ nullptr, 0, 0, 0, 0 }, "aomhip_warp_affine_batch");
+                     ConvBuf{ nullptr, 0, 0, 0, 0 }, "aomhip_warp_affine_batch");
 }
 
 extern "C" int aomhip_warp_affine_compound_batch(aomhip_ctx *ctx, const aomhip_planes *ref, int ref_frame, const aomhip_planes *pred, int pred_frame,
@@ -252,7 +236,7 @@ extern "C" int aomhip_warp_affine_compound_batch(aomhip_ctx *ctx, const aomhip_p
                                                  int max_block_height, uint16_t *d_conv, int conv_stride, int do_average, int use_dist_wtd_comp_avg,
                                                  int fwd_offset, int bck_offset) {
   return warp_launch(ctx, ref, ref_frame, do_average ? pred : nullptr, pred_frame, subsampling_x, subsampling_y, d_blocks, n_blocks, max_block_width,
-                     max_block_height, do_average ? 2 : 1, WarpCompound{ d_conv, conv_stride, use_dist_wtd_comp_avg, fwd_offset, bck_offset },
+                     max_block_height, do_average ? 2 : 1, ConvBuf{ d_conv, conv_stride, use_dist_wtd_comp_avg, fwd_offset, bck_offset },
                      "aomhip_warp_affine_compound_batch");
 }
 
