@@ -146,6 +146,12 @@ lr_pick_params_dtype = np.dtype([("rdmult", "<i4"), ("wiener_restore_cost", "<i4
                                  ("prune_sgr_based_on_wiener", "<i4"), ("dual_sgr_penalty_level", "<i4"), ("wiener_src_var_thresh", "<u8")])
 lr_unit_search_dtype = np.dtype([("sse", "<i8", (3,)), ("best_rtype", "<i4", (3,)), ("skip_sgr_eval", "<i4"), ("wiener_sgr", lr_unit_info_dtype)])
 lr_plane_pick_dtype = np.dtype([("frame_restoration_type", "<i4"), ("searched", "<i4"), ("cost", "<f8", (4,)), ("bits", "<i8", (4,)), ("sse", "<i8", (4,))])
+# aomhip_cdef_pick (152 bytes) / aomhip_cdef_pick_trace (16 bytes): aomhip_cdef_pick_strengths, aomhip_cdef_search_frame
+CDEF_PICK_MAX_CALLS = 75
+CDEF_FB_64, CDEF_FB_128X128, CDEF_FB_128X64, CDEF_FB_64X128 = range(4)
+cdef_pick_dtype = np.dtype([("cdef_bits", "<i4"), ("nb_cdef_strengths", "<i4"), ("cdef_strengths", "<i4", (8,)), ("cdef_uv_strengths", "<i4", (8,)),
+                            ("sb_count", "<i4"), ("reserved", "<i4"), ("best_rd", "<u8"), ("tot_mse", "<u8", (4,)), ("rd", "<u8", (4,))])
+cdef_pick_trace_dtype = np.dtype([("id0", "<i4"), ("id1", "<i4"), ("best_tot_mse", "<u8")])
 scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_qn", "subpel_y_qn", "dst_x", "dst_y")])   # aomhip_scaled_block
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
@@ -157,6 +163,20 @@ warp_refine_block_dtype = np.dtype([(n_, "<i2") for n_ in ("bx", "by", "mv_row",
 warp_refine_result_dtype = np.dtype([("mv_row", "<i2"), ("mv_col", "<i2"), ("num_proj_ref", "<i4"), ("bestmse", "<u4"), ("model", warp_model_dtype)])
 warp_block_dtype = np.dtype([("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("p_col", "<i4"), ("p_row", "<i4"),
                              ("p_width", "<i4"), ("p_height", "<i4")])   # aomhip_warp_block (48 bytes)
+
+
+class CdefSearchIn(C.Structure):
+    """aomhip_cdef_search_in (include/aomhip.h)."""
+    _fields_ = [("recon", C.POINTER(Planes) * 3), ("source", C.POINTER(Planes) * 3), ("recon_frame", C.c_int32), ("source_frame", C.c_int32),
+                ("xdec", C.c_int32), ("ydec", C.c_int32), ("d_strengths", C.c_void_p), ("n_strengths", C.c_int32), ("fast", C.c_int32),
+                ("d_skip8x8", C.c_void_p), ("d_fb_class", C.c_void_p), ("damping", C.c_int32), ("rdmult", C.c_int32), ("fb_stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class CdefSearchOut(C.Structure):
+    """aomhip_cdef_search_out (include/aomhip.h)."""
+    _fields_ = [(n_, C.c_void_p) for n_ in ("d_fb_index", "d_fb_pri", "d_fb_sec", "d_fb_uv_pri", "d_fb_uv_sec", "d_pick", "d_dir_out", "d_var_out", "d_mse0",
+                                            "d_mse1", "d_entry_fb")]
 
 
 class CompoundParams(C.Structure):
@@ -305,6 +325,8 @@ _protos = {
     "aomhip_wedge_compute_delta_squares_batch": (C.c_int, [_vp, _vp, _vp, _i, _i, _vp]),
     "aomhip_cdef_search_sse_luma": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "aomhip_cdef_search_sse_chroma": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "aomhip_cdef_pick_strengths": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "aomhip_cdef_search_frame": (C.c_int, [_vp, _vp, _vp]),
     "aomhip_lpf_search_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _vp, _i64, _i, _i, _i, _i, _vp]),
     "aomhip_compute_stats_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_plane_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp]),
@@ -1036,6 +1058,26 @@ class Context:
                                fb_stride, d_sse):
         check(lib.aomhip_cdef_search_sse_chroma(self.h, C.byref(recon), recon_frame, C.byref(source), source_frame, xdec, ydec, d_luma_dir,
                                                 d_strengths, n, d_skip, damping, fb_stride, d_sse), "aomhip_cdef_search_sse_chroma")
+
+    def cdef_pick_strengths(self, d_mse0, d_mse1, d_sb_count, sb_capacity, d_strengths, n, fast, rdmult, d_pick, d_entry_gi, d_trace=None):
+        """The decision of av1_cdef_search on device tables [entry][n] (d_mse1 None: monochrome); d_pick: one cdef_pick_dtype record, d_entry_gi: int8 per
+        entry, d_trace: CDEF_PICK_MAX_CALLS cdef_pick_trace_dtype records or None."""
+        check(lib.aomhip_cdef_pick_strengths(self.h, d_mse0, d_mse1, d_sb_count, sb_capacity, d_strengths, n, fast, rdmult, d_pick, d_entry_gi, d_trace),
+              "aomhip_cdef_pick_strengths")
+
+    def cdef_search_frame(self, recon, recon_frame, source, source_frame, xdec, ydec, d_strengths, n, fast, d_skip, damping, rdmult, fb_stride, d_fb_index,
+                          d_fb_pri, d_fb_sec, d_pick, d_fb_uv_pri=None, d_fb_uv_sec=None, d_fb_class=None, d_dir=None, d_var=None, d_mse0=None, d_mse1=None,
+                          d_entry_fb=None):
+        """av1_cdef_search from the planes: recon / source are sequences of the Y, U, V rings (one ring: monochrome)."""
+        a, o = CdefSearchIn(), CdefSearchOut()
+        for k in range(3):
+            a.recon[k] = C.pointer(recon[k]) if k < len(recon) and recon[k] is not None else None
+            a.source[k] = C.pointer(source[k]) if k < len(source) and source[k] is not None else None
+        a.recon_frame, a.source_frame, a.xdec, a.ydec, a.d_strengths, a.n_strengths, a.fast = recon_frame, source_frame, xdec, ydec, d_strengths, n, fast
+        a.d_skip8x8, a.d_fb_class, a.damping, a.rdmult, a.fb_stride = d_skip, d_fb_class, damping, rdmult, fb_stride
+        o.d_fb_index, o.d_fb_pri, o.d_fb_sec, o.d_fb_uv_pri, o.d_fb_uv_sec, o.d_pick = d_fb_index, d_fb_pri, d_fb_sec, d_fb_uv_pri, d_fb_uv_sec, d_pick
+        o.d_dir_out, o.d_var_out, o.d_mse0, o.d_mse1, o.d_entry_fb = d_dir, d_var, d_mse0, d_mse1, d_entry_fb
+        check(lib.aomhip_cdef_search_frame(self.h, C.byref(a), C.byref(o)), "aomhip_cdef_search_frame")
 
     def lpf_search_sse(self, recon, recon_frame, scratch, scratch_frame, source, source_frame, d_params, trial_stride, n_trials, units_stride,
                        sharpness, passes, d_sse):

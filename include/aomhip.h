@@ -568,8 +568,8 @@ int aomhip_cdef_luma_plane(aomhip_ctx *ctx, const aomhip_planes *src, int src_fr
  *                 (sec_strength == 3)`, :439); get_cdef_filter_strengths (:29-84) gives the list for a pick method
  *   d_sse         [n_strengths][n_fb_rows * fb_stride] RAW sums.  The reference stores `sum >> 2 * coeff_shift` for
  *                 high-bit-depth frames (:260) and merges the filter blocks of a 128-wide superblock into one entry
- *                 (:541-556) before shifting, so both steps are the caller's: mse[0][sb][gi] = (sum of its blocks) >>
- *                 2 * (bit_depth - 8).
+ *                 (:541-556) before shifting: mse[0][sb][gi] = (sum of its blocks) >> 2 * (bit_depth - 8).
+ *                 aomhip_cdef_search_frame does both on the device, together with the list of searched blocks.
  *   d_dir_out / d_var_out  as aomhip_cdef_luma_plane (the chroma search reuses the directions). */
 int aomhip_cdef_search_sse_luma(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *source,
                                 int source_frame, const uint8_t *d_strengths, int n_strengths, const uint8_t *d_skip8x8, int damping,
@@ -578,10 +578,97 @@ int aomhip_cdef_search_sse_luma(aomhip_ctx *ctx, const aomhip_planes *recon, int
 /* The same table for a CHROMA plane (pli > 0: no variance adjustment, damping - 1, the luma directions; get_filt_error with
  * xdec / ydec, pickcdef.c:401-501).  d_luma_dir = the d_dir_out of the luma call; a filter block is (64 >> xdec) x
  * (64 >> ydec) and a unit (8 >> xdec) x (8 >> ydec).  The reference's mse[1][sb][gi] is (U sums >> 2 * coeff_shift) +
- * (V sums >> 2 * coeff_shift) (:603-606): call once per plane and combine on the host. */
+ * (V sums >> 2 * coeff_shift) (:603-606): call once per plane; aomhip_cdef_search_frame combines them on the device. */
 int aomhip_cdef_search_sse_chroma(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *source,
                                   int source_frame, int xdec, int ydec, const uint8_t *d_luma_dir, const uint8_t *d_strengths,
                                   int n_strengths, const uint8_t *d_skip8x8, int damping, int fb_stride, uint64_t *d_sse);
+
+/* The decision of av1_cdef_search on given distortion tables: the loop over the number of signalling bits and its tail
+ * (av1/encoder/pickcdef.c:862-937) as one stream-ordered call that reads its tables from device memory --
+ * joint_strength_search_dual (:199-224: the greedy search, then 4 * nb_strengths refinement calls, also for the fast methods)
+ * or, for monochrome, joint_strength_search (:172-196: no refinement when `fast`) for 1 / 2 / 4 / 8 strengths while
+ * i <= max_signaling_bits (:872-878); search_one / search_one_dual (:86-169) start from 1 << 63, compare with strict `<`
+ * (the first minimum in (j, k) raster order wins); total_bits, av1_cost_literal, dist = tot_mse * 16, RDCOST and
+ * `rd < best_rd` (:891-905); per entry the first best gi among the winner's strengths (:910-923).
+ *   d_mse0 / d_mse1  uint64 [entry][n_strengths]: mse[0] (luma) and mse[1] (U + V).  d_mse1 == NULL: monochrome
+ *                    (num_planes == 1).  Behaviour is pinned for tables whose column sums stay below 2^63 (the reference's
+ *                    sentinel); beyond that sums wrap as uint64_t sums do.
+ *   d_sb_count       ONE device int32: the number of entries (cdef_search_ctx.sb_count), read by the kernels; values outside
+ *                    0 .. sb_capacity are clamped.  sb_capacity: a host bound on it that sizes the launches.
+ *   d_strengths      n_strengths (1 .. 64) byte pairs { pri, sec }, sec mapped 3 -> 4, as the SSE calls take them
+ *   fast             pick_method in CDEF_FAST_SEARCH_LVL1 .. LVL5 (:840-841)
+ *   d_pick           the record below.  cdef_strengths[] / cdef_uv_strengths[] hold pri * CDEF_SEC_STRENGTHS + sec with sec
+ *                    unmapped (4 -> 3) of the chosen list entries: STORE_CDEF_FILTER_STRENGTH (:77-82, :924-935), the identity
+ *                    for the full list and therefore applied always; 0 past nb_cdef_strengths; uv all 0 for monochrome.
+ *   d_entry_gi       one int8 per entry < sb_count: mbmi->cdef_strength (:921)
+ *   d_trace          optional: { id0, id1, best_tot_mse } of every search_one[_dual] call in call order (at most
+ *                    AOMHIP_CDEF_PICK_MAX_CALLS; id1 = 0 for monochrome) -- an intermediate a later step may repair
+ * The number of launches depends on (n_strengths, planes, fast) only; no synchronisation and no device -> host copy once the
+ * work memory exists (growing it synchronises: run the call once before capturing it).  Refused: n_strengths outside
+ * 1 .. 64, sb_capacity < 0, a missing pointer. */
+#define AOMHIP_CDEF_PICK_MAX_CALLS 75 /* 5 * (1 + 2 + 4 + 8) */
+typedef struct {
+  int32_t cdef_bits, nb_cdef_strengths;              /* cdef_info->cdef_bits, ->nb_cdef_strengths (:908-909) */
+  int32_t cdef_strengths[8], cdef_uv_strengths[8];   /* the search fills at most 1 << 3 of the CDEF_MAX_STRENGTHS slots */
+  int32_t sb_count, reserved;
+  uint64_t best_rd;
+  uint64_t tot_mse[4], rd[4];                        /* per i (:882-895); UINT64_MAX where i was not tried */
+} aomhip_cdef_pick;           /* 152 bytes */
+typedef struct {
+  int32_t id0, id1;
+  uint64_t best_tot_mse;
+} aomhip_cdef_pick_trace;     /* 16 bytes */
+int aomhip_cdef_pick_strengths(aomhip_ctx *ctx, const uint64_t *d_mse0, const uint64_t *d_mse1, const int32_t *d_sb_count, int sb_capacity,
+                               const uint8_t *d_strengths, int n_strengths, int fast, int rdmult, aomhip_cdef_pick *d_pick, int8_t *d_entry_gi,
+                               aomhip_cdef_pick_trace *d_trace);
+
+/* av1_cdef_search (av1/encoder/pickcdef.c:819-940, without CDEF_PICK_FROM_Q, the CDEF_REFERENCE early return and the
+ * multithreaded variant) from the planes, entirely on the context's stream: the three distortion tables through
+ * aomhip_cdef_search_sse_luma / _chroma, the entry list of cdef_mse_calc_frame + cdef_sb_skip + av1_cdef_mse_calc_block
+ * (:518-629, pickcdef.h:197-214), aomhip_cdef_pick_strengths on it, and the per-filter-block levels the filter calls take.
+ * The entry count never leaves the device.
+ *   recon / source     rings of Y, U, V (the deblocked reconstruction and the source frame): Y rings of one geometry and bit
+ *                      depth, multiples of 8; U and V rings of the subsampled geometry and the same depth, or both NULL for
+ *                      monochrome.  recon_frame / source_frame index every ring of their side.
+ *   d_fb_class         optional, one byte per 64x64 filter block (fb_stride per row): mbmi->bsize of its top-left mode info as
+ *                      AOMHIP_CDEF_FB_64 / _128X128 / _128X64 / _64X128 (W x H).  NULL: all 64.
+ *   entries            raster order over filter blocks; a block is left out when every 8x8 unit of it is skip (sb_all_skip) or
+ *                      when it is the odd column (row) under its OWN class 128X128 / 128X64 (128X128 / 64X128).  An entry of a
+ *                      128 class sums the RAW sums of the hb_step x vb_step filter blocks it covers, clipped at the frame; each
+ *                      plane's sum is shifted by 2 * (bit_depth - 8) after the merge, U and V separately, then added (:601-606).
+ *   d_fb_index         int8 per filter block (fb_stride per row, columns < the frame's count): the entry's cdef_strength for
+ *                      every block the entry covers (they share one MB_MODE_INFO), -1 for a block in no entry.  A DEVIATION:
+ *                      the reference leaves such a block's cdef_strength untouched; its filter skips the block anyway
+ *                      (av1/common/cdef.c:301-306) and aomhip_cdef_build_strengths reads -1 that way.  A block that is not
+ *                      an entry looks for its entry to the left (odd column), above (odd row), above-left, in that order.
+ *   d_fb_pri .. d_fb_uv_sec   what aomhip_cdef_build_strengths gives for d_fb_index and the record, written on the device so
+ *                      that aomhip_cdef_luma_plane / _chroma_plane can follow in the same stream or captured graph.  The uv
+ *                      pair may be NULL.
+ *   d_dir_out / d_var_out     as the luma SSE call gives them; both optional (the chroma tables read work memory then).
+ *   d_mse0 / d_mse1 / d_entry_fb   optional: the compacted tables [entry][n_strengths] and fbr * fb_stride + fbc of every
+ *                      entry, n_fb_rows * fb_stride rows / ints of room.
+ * Refused as the SSE calls refuse: mismatched bit depths or geometries, n_strengths outside 1 .. 64, damping outside 3 .. 6,
+ * only one of U and V, a bad frame index, fb_stride below the frame's count.  Work memory: as aomhip_cdef_pick_strengths. */
+enum { AOMHIP_CDEF_FB_64 = 0, AOMHIP_CDEF_FB_128X128 = 1, AOMHIP_CDEF_FB_128X64 = 2, AOMHIP_CDEF_FB_64X128 = 3 };
+typedef struct {
+  const aomhip_planes *recon[3], *source[3];
+  int32_t recon_frame, source_frame;
+  int32_t xdec, ydec;                 /* of U and V */
+  const uint8_t *d_strengths;
+  int32_t n_strengths, fast;
+  const uint8_t *d_skip8x8, *d_fb_class;
+  int32_t damping, rdmult, fb_stride, reserved;
+} aomhip_cdef_search_in;
+typedef struct {
+  int8_t *d_fb_index;
+  uint8_t *d_fb_pri, *d_fb_sec, *d_fb_uv_pri, *d_fb_uv_sec;
+  aomhip_cdef_pick *d_pick;
+  uint8_t *d_dir_out;
+  int32_t *d_var_out;
+  uint64_t *d_mse0, *d_mse1;
+  int32_t *d_entry_fb;
+} aomhip_cdef_search_out;
+int aomhip_cdef_search_frame(aomhip_ctx *ctx, const aomhip_cdef_search_in *in, const aomhip_cdef_search_out *out);
 
 /* The same for a CHROMA plane (pli > 0 in av1_cdef_filter_fb, cdef_block.c:323-426): `src` / `dst` are rings of that
  * chroma plane, xdec / ydec its subsampling (4:2:0 = 1,1; 4:4:4 = 0,0; 4:2:2 = 1,0; 4:4:0 = 0,1), so one luma 8x8
