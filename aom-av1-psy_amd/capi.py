@@ -179,6 +179,35 @@ class CdefSearchOut(C.Structure):
                                             "d_mse1", "d_entry_fb")]
 
 
+# aomhip_lf_search_unit (8 bytes): the level-free unit record of the filter-level search (aomhip_lf_edge_params_device, aomhip_lpf_level_sse_table)
+lf_search_unit_dtype = np.dtype([("tx_size", "u1"), ("skip_inter", "u1"), ("pb_w_log2", "u1"), ("pb_h_log2", "u1"), ("segment_id", "u1"), ("ref_mode", "u1"),
+                                 ("delta_lf_v", "i1"), ("delta_lf_h", "i1")])
+LPF_PICK_FROM_FULL_IMAGE, LPF_PICK_FROM_FULL_IMAGE_NON_DUAL, LPF_PICK_FROM_SUBIMAGE = range(3)
+LPF_TRACE_INTS = 65
+
+
+class LfFrameParams(C.Structure):
+    """aomhip_lf_frame_params (include/aomhip.h)."""
+    _fields_ = [("filter_level", C.c_int * 2), ("filter_level_u", C.c_int), ("filter_level_v", C.c_int), ("mode_ref_delta_enabled", C.c_int),
+                ("ref_deltas", C.c_int8 * 8), ("mode_deltas", C.c_int8 * 2), ("seg_enabled", C.c_int), ("seg_feature_mask", C.c_uint8 * 8),
+                ("seg_feature_data", (C.c_int16 * 8) * 8)]
+
+
+class LpfPickIn(C.Structure):
+    """aomhip_lpf_pick_in (include/aomhip.h)."""
+    _fields_ = [("recon", C.POINTER(Planes) * 3), ("source", C.POINTER(Planes) * 3), ("recon_frame", C.c_int32), ("source_frame", C.c_int32),
+                ("xdec", C.c_int32), ("ydec", C.c_int32), ("d_units", C.c_void_p * 3), ("units_stride", C.c_int32 * 3), ("delta_lf_present", C.c_int32),
+                ("fp", C.POINTER(LfFrameParams)), ("method", C.c_int32), ("max_level", C.c_int32), ("coarse", C.c_int32), ("twopass_consumption", C.c_int32),
+                ("section_intra_rating", C.c_int32), ("only_4x4", C.c_int32), ("mi_rows", C.c_int32), ("reserved", C.c_int32),
+                ("last_frame_filter_level", C.c_int32 * 4)]
+
+
+class LpfPickOut(C.Structure):
+    """aomhip_lpf_pick_out (include/aomhip.h)."""
+    _fields_ = [("d_levels", C.c_void_p), ("d_edge_params", C.c_void_p * 3), ("edge_stride", C.c_int32 * 3), ("reserved", C.c_int32), ("d_tables", C.c_void_p),
+                ("d_traces", C.c_void_p)]
+
+
 class CompoundParams(C.Structure):
     """aomhip_compound_params (include/aomhip.h)."""
     _fields_ = [("kind", C.c_int32), ("subpel", C.c_int32), ("fwd_offset", C.c_int32), ("bck_offset", C.c_int32),
@@ -328,6 +357,10 @@ _protos = {
     "aomhip_cdef_pick_strengths": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "aomhip_cdef_search_frame": (C.c_int, [_vp, _vp, _vp]),
     "aomhip_lpf_search_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _PP, _i, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "aomhip_lf_edge_params_device": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _i]),
+    "aomhip_lpf_level_sse_table": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "aomhip_lpf_pick_level": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "aomhip_pick_filter_level_frame": (C.c_int, [_vp, _vp, _vp]),
     "aomhip_compute_stats_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_plane_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp]),
     "aomhip_build_inter_pred_ex_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i]),
@@ -1083,6 +1116,44 @@ class Context:
                        sharpness, passes, d_sse):
         check(lib.aomhip_lpf_search_sse(self.h, C.byref(recon), recon_frame, C.byref(scratch), scratch_frame, C.byref(source), source_frame,
                                         d_params, trial_stride, n_trials, units_stride, sharpness, passes, d_sse), "aomhip_lpf_search_sse")
+
+    def lf_edge_params_device(self, d_units, units_stride, width, height, plane, ssy, fp, delta_lf_present, d_levels, d_edge_params, edge_stride,
+                              mi_rows=(0, -1)):
+        """aomhip_lf_level_table + aomhip_lf_build_edge_params on the device for base levels in device memory (fp: LfFrameParams)."""
+        check(lib.aomhip_lf_edge_params_device(self.h, d_units, units_stride, width, height, plane, ssy, C.byref(fp), delta_lf_present, d_levels, mi_rows[0],
+                                               mi_rows[1], d_edge_params, edge_stride), "aomhip_lf_edge_params_device")
+
+    def lpf_level_sse_table(self, recon, recon_frame, source, source_frame, d_units, units_stride, plane, ssy, dir_, fp, delta_lf_present, d_levels, max_level,
+                            sharpness, d_ss_err, mi_rows=(0, -1)):
+        """try_filter_frame for every level 0 .. max_level of one (plane, dir): d_ss_err int64[64]."""
+        check(lib.aomhip_lpf_level_sse_table(self.h, C.byref(recon), recon_frame, C.byref(source), source_frame, d_units, units_stride, plane, ssy, dir_,
+                                             C.byref(fp), delta_lf_present, d_levels, mi_rows[0], mi_rows[1], max_level, sharpness, d_ss_err),
+              "aomhip_lpf_level_sse_table")
+
+    def lpf_pick_level(self, d_ss_err, max_level, start_level, d_levels, slot_mask, coarse=0, twopass=0, rating=0, only_4x4=0, d_start=None, d_trace=None):
+        """search_filter_level's walk on a device table; the level goes to d_levels[s] for every bit s of slot_mask."""
+        check(lib.aomhip_lpf_pick_level(self.h, d_ss_err, max_level, start_level, d_start, coarse, twopass, rating, only_4x4, d_levels, slot_mask, d_trace),
+              "aomhip_lpf_pick_level")
+
+    def pick_filter_level_frame(self, recon, recon_frame, source, source_frame, xdec, ydec, d_units, units_stride, fp, delta_lf_present, method, max_level,
+                                mi_rows, last_levels, d_levels, coarse=0, twopass=0, rating=0, only_4x4=0, d_edge_params=(None, None, None),
+                                edge_stride=(0, 0, 0), d_tables=None, d_traces=None):
+        """av1_pick_filter_level's search branch from the planes: recon / source / d_units are sequences over Y, U, V (one ring: monochrome)."""
+        a, o = LpfPickIn(), LpfPickOut()
+        for k in range(3):
+            a.recon[k] = C.pointer(recon[k]) if k < len(recon) and recon[k] is not None else None
+            a.source[k] = C.pointer(source[k]) if k < len(source) and source[k] is not None else None
+            a.d_units[k] = d_units[k] if k < len(d_units) else None
+            a.units_stride[k] = units_stride[k] if k < len(units_stride) else 0
+            o.d_edge_params[k] = d_edge_params[k] if k < len(d_edge_params) else None
+            o.edge_stride[k] = edge_stride[k] if k < len(edge_stride) else 0
+        a.recon_frame, a.source_frame, a.xdec, a.ydec, a.delta_lf_present = recon_frame, source_frame, xdec, ydec, delta_lf_present
+        a.fp = C.cast(C.pointer(fp), C.POINTER(LfFrameParams))      # (any ctypes structure of the header's layout)
+        a.method, a.max_level, a.coarse, a.twopass_consumption, a.section_intra_rating, a.only_4x4, a.mi_rows = method, max_level, coarse, twopass, rating, only_4x4, mi_rows
+        for k in range(4):
+            a.last_frame_filter_level[k] = last_levels[k]
+        o.d_levels, o.d_tables, o.d_traces = d_levels, d_tables, d_traces
+        check(lib.aomhip_pick_filter_level_frame(self.h, C.byref(a), C.byref(o)), "aomhip_pick_filter_level_frame")
 
     def compute_stats_batch(self, dgd, dgd_frame, src, src_frame, win, d_units, h_units, n, downsample, d_M, d_H):
         hp = h_units.ctypes.data if h_units is not None else None

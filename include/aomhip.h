@@ -539,6 +539,118 @@ int aomhip_lpf_search_sse(aomhip_ctx *ctx, const aomhip_planes *recon, int recon
                           const aomhip_planes *source, int source_frame, const uint8_t *d_edge_params, int64_t trial_stride, int n_trials,
                           int units_stride, int sharpness, int passes, uint64_t *d_sse);
 
+/* ---- av1_pick_filter_level's search on the device (csrc/lpf_pick.hip).  aomhip_lf_frame_params is declared with the host producers below. */
+struct aomhip_lf_frame_params_s;
+
+/* The level-FREE description of a 4x4 unit of a plane, uploaded once per frame and plane: what aomhip_lf_unit holds without the
+ * resolved levels, and what av1_get_filter_level (av1/common/av1_loopfilter.c:68-107) reads of the mode info instead.
+ *   tx_size, skip_inter, pb_w_log2, pb_h_log2   as in aomhip_lf_unit
+ *   segment_id   mbmi->segment_id (0 .. 7)
+ *   ref_mode     mbmi->ref_frame[0] (0 .. 7, INTRA_FRAME = 0) | mode_lf_lut[mbmi->mode] << 3 (:41-45)
+ *   delta_lf_v / _h   what :73-79 adds for this plane and edge direction: mbmi->delta_lf_from_base, or
+ *                mbmi->delta_lf[delta_lf_id_lut[plane][dir]] under delta_lf_multi; read only with delta_lf_present */
+typedef struct {
+  uint8_t tx_size, skip_inter, pb_w_log2, pb_h_log2, segment_id, ref_mode;
+  int8_t delta_lf_v, delta_lf_h;
+} aomhip_lf_search_unit;      /* 8 bytes, 8-byte aligned in device memory */
+
+/* aomhip_lf_level_table + aomhip_lf_build_edge_params in one stream-ordered launch: av1_get_filter_level (:68-107, both branches:
+ * the scale 1 << (lvl_seg >> 5), the clamps in their order, the mode delta only for ref_frame[0] > INTRA_FRAME) and
+ * set_lpf_parameters (:223-328, as one_edge() of host/filter_maps.c) at every unit, for base levels READ FROM DEVICE MEMORY:
+ * d_levels[4] = cm->lf.filter_level[0], [1], filter_level_u, filter_level_v (each clamped to 0 .. 63).  `fp` is read on the host at
+ * call time for the reference / mode deltas and the segment features; its four filter_level* members are ignored.
+ * The plane rule of check_planes_to_loop_filter (av1/common/thread_common.h:302-315) with av1_loop_filter_frame_init's early-outs
+ * (av1_loopfilter.c:152-158) is part of it: luma gets all-zero records when both its levels are 0, U when filter_level_u is 0, V when
+ * filter_level_v is 0, whatever the deltas would make of it; with one luma level 0 and the other not, deltas apply to base 0.
+ * (The reference also skips chroma when luma is not filtered IN THE SAME call, thread_common.h:313; the planes are separate calls
+ * here as they are in try_filter_frame, so that stays with the caller.)
+ *   plane / ssy   0 .. 2 and the plane's vertical subsampling (0 for luma): unit row uy holds mode-info row uy << ssy
+ *   mi_row_start / mi_row_end   av1_loop_filter_frame_mt's partial frame (thread_common.c:411-418): records of unit rows outside
+ *                 [start, end) are zero.  mi_row_end < 0: the whole plane.
+ *   d_edge_params the { len_v, lvl_v, len_h, lvl_h } plane aomhip_deblock_plane[_fused] takes, 4-byte aligned
+ * A unit with ref_frame[0] == INTRA_FRAME and mode_lf 1 does not occur (mode_lf_lut is 0 for the intra modes); it is computed
+ * by the formula, without the mode delta.
+ * Refused: a missing pointer, plane / ssy out of range, a stride below the plane's unit count, a negative or reversed row range. */
+int aomhip_lf_edge_params_device(aomhip_ctx *ctx, const aomhip_lf_search_unit *d_units, int units_stride, int plane_width, int plane_height,
+                                 int plane, int ssy, const struct aomhip_lf_frame_params_s *fp, int delta_lf_present, const int32_t *d_levels,
+                                 int mi_row_start, int mi_row_end, uint8_t *d_edge_params, int edge_stride);
+
+/* try_filter_frame (av1/encoder/picklpf.c:49-86) for EVERY level of one search_filter_level call (:88-193), one launch:
+ * d_ss_err[L], L = 0 .. max_level, is aom_get_sse_plane of the source against the plane deblocked with the records
+ * aomhip_lf_edge_params_device gives for that trial's base levels (:58-70) --
+ *   luma, dir 2: both directions L;  dir 0: vertical edges L, horizontal d_levels[1];  dir 1: vertical d_levels[0], horizontal L;
+ *   plane 1 / 2 (dir must be 0): L
+ * -- under the plane rule and the row range above.  The fixed level is read from device memory when the kernel runs: what the
+ * previous search's aomhip_lpf_pick_level wrote.  try_filter_frame is a pure function of the trial level, so the table holds
+ * exactly what the reference's lazily filled ss_err[] would.  Entries above max_level (<= 63: av1_get_max_filter_level, :40-47)
+ * are -1.  Nothing else is written: the reconstruction stays untouched and no scratch plane is needed.  A workgroup stages a
+ * 128x64 tile, its halo, the source tile and the unit records once and runs its levels from LDS (deblock_fused_kernel's passes).
+ * sharpness: lf->sharpness_level (av1_pick_filter_level sets 0, :204).  No border or alignment is required of the planes.
+ * Refused: reconstruction and source of different geometry or depth, a bad frame index, units_stride below the plane's unit
+ * count, max_level outside 0 .. 63, dir outside 0 .. 2 or non-zero for a chroma plane, a missing pointer. */
+int aomhip_lpf_level_sse_table(aomhip_ctx *ctx, const aomhip_planes *recon, int recon_frame, const aomhip_planes *source, int source_frame,
+                               const aomhip_lf_search_unit *d_units, int units_stride, int plane, int ssy, int dir,
+                               const struct aomhip_lf_frame_params_s *fp, int delta_lf_present, const int32_t *d_levels, int mi_row_start,
+                               int mi_row_end, int max_level, int sharpness, int64_t *d_ss_err);
+
+/* search_filter_level's walk (picklpf.c:118-192) on a table in device memory, one small launch: filt_mid = clamp(start, 0,
+ * max_level); filter_step = filt_mid < 16 ? 4 : filt_mid / 4; stop threshold 0, or 2 with `coarse`
+ * (sf.lpf_sf.use_coarse_filter_level_search); bias = (best_err >> (15 - filt_mid / 8)) * filter_step in 64 bits, scaled by
+ * section_intra_rating / 20 when twopass_consumption (is_stat_consumption_stage_twopass) and the rating is below 20, halved unless
+ * only_4x4 (tx_mode == ONLY_4X4); low before high, `< best_err + bias` below and `< best_err - bias` above, filt_direction.
+ *   start_level / d_start   the start: *d_start if d_start is not NULL (device memory, e.g. a slot of d_levels), else start_level
+ *   d_levels / slot_mask    the result is written to d_levels[s] for every bit s of slot_mask (1 .. 15)
+ *   d_trace      optional, AOMHIP_LPF_TRACE_INTS int32: [0] = the number of try_filter_frame calls the reference would have
+ *                made, [1 ..] their levels in call order (a level requested again is not tried again, :153,:170)
+ * Refused: max_level outside 0 .. 63, slot_mask outside 1 .. 15, a missing pointer. */
+#define AOMHIP_LPF_TRACE_INTS 65
+int aomhip_lpf_pick_level(aomhip_ctx *ctx, const int64_t *d_ss_err, int max_level, int start_level, const int32_t *d_start, int coarse,
+                          int twopass_consumption, int section_intra_rating, int only_4x4, int32_t *d_levels, int slot_mask, int32_t *d_trace);
+
+/* av1_pick_filter_level's search branch (picklpf.c:289-327) from the planes, entirely on the context's stream: per
+ * search_filter_level call one table launch and one walk launch -- luma dir 2 into both luma levels; unless NON_DUAL, dir 0 with
+ * the horizontal level fixed at that result, then dir 1 with the vertical level fixed at the dir 0 result; then U and V unless
+ * monochrome -- then aomhip_lf_edge_params_device for the chosen levels.  sharpness_level is 0 (:204).
+ * OUT OF SCOPE, left with the caller: LPF_PICK_FROM_Q and LPF_PICK_MINIMAL_LPF (closed-form host arithmetic on qindex, :220-288),
+ * the loopfilter_control / screen-content early returns (:206-218), and the zeros that go in for intra-only frames (:290-296).
+ *   recon / source   rings of Y, U, V (the unfiltered reconstruction and the source): per plane one geometry and bit depth; U and V
+ *                    of the subsampled geometry and the luma depth, or both NULL for monochrome (filter_level_u / _v stay untouched)
+ *   d_units / units_stride   the search units of each plane
+ *   fp, delta_lf_present     as aomhip_lf_edge_params_device
+ *   method           AOMHIP_LPF_PICK_FROM_FULL_IMAGE, _NON_DUAL, or _FROM_SUBIMAGE: the trials filter the partial frame of
+ *                    thread_common.c:411-418 as the reference's row loop filters it (:384: whole 32-row superblock rows from the
+ *                    start row, clipped at mi_rows); the final edge-parameter planes are always for the whole frame
+ *   max_level, coarse, twopass_consumption, section_intra_rating, only_4x4   as aomhip_lpf_pick_level
+ *   last_frame_filter_level  the starts (:290-296); the dir 2 start is (l0 + l1 + 1) >> 1
+ *   d_levels         int32[4] out: filter_level[0], [1], filter_level_u, filter_level_v
+ *   d_edge_params    optional per plane: the records for the chosen levels, for aomhip_deblock_plane[_fused] in the same stream
+ *   d_tables         optional int64 [5][64]: the tables in the order Y dir 2, Y dir 0, Y dir 1, U, V (zero where no search ran)
+ *   d_traces         optional int32 [5][AOMHIP_LPF_TRACE_INTS], same order (untouched where no search ran)
+ * The launch sequence depends on (method, planes) only; no synchronisation and no device -> host copy once the work memory exists
+ * (without d_tables the first call may grow it: run the call once before capturing it).
+ * Refused: mismatched geometries or bit depths, only one of U and V, a bad frame index, a stride below the plane's unit count,
+ * max_level outside 0 .. 63, an unknown method, a missing pointer. */
+enum { AOMHIP_LPF_PICK_FROM_FULL_IMAGE = 0, AOMHIP_LPF_PICK_FROM_FULL_IMAGE_NON_DUAL = 1, AOMHIP_LPF_PICK_FROM_SUBIMAGE = 2 };
+typedef struct {
+  const aomhip_planes *recon[3], *source[3];
+  int32_t recon_frame, source_frame;
+  int32_t xdec, ydec;                 /* of U and V */
+  const aomhip_lf_search_unit *d_units[3];
+  int32_t units_stride[3];
+  int32_t delta_lf_present;
+  const struct aomhip_lf_frame_params_s *fp;
+  int32_t method, max_level, coarse, twopass_consumption, section_intra_rating, only_4x4, mi_rows, reserved;
+  int32_t last_frame_filter_level[4];
+} aomhip_lpf_pick_in;         /* 160 bytes */
+typedef struct {
+  int32_t *d_levels;
+  uint8_t *d_edge_params[3];
+  int32_t edge_stride[3], reserved;
+  int64_t *d_tables;
+  int32_t *d_traces;
+} aomhip_lpf_pick_out;        /* 64 bytes */
+int aomhip_pick_filter_level_frame(aomhip_ctx *ctx, const aomhip_lpf_pick_in *in, const aomhip_lpf_pick_out *out);
+
 /* ------------------------------------------------------------------ CDEF */
 
 /* av1_cdef_frame (av1/common/cdef.c:440) for the LUMA plane, out of place: frame `src_frame` of `src` is the
@@ -1917,7 +2029,7 @@ int aomhip_lf_build_edge_params(const aomhip_lf_unit *units, int units_stride, i
 
 /* av1_loop_filter_frame_init (av1_loopfilter.c:126-195) for one plane: lvl[segment][dir][ref_frame][mode_lf_lut[mode]], what
  * av1_get_filter_level returns when cm->delta_q_info.delta_lf_present_flag is 0. */
-typedef struct {
+typedef struct aomhip_lf_frame_params_s {
   int filter_level[2], filter_level_u, filter_level_v; /* cm->lf */
   int mode_ref_delta_enabled;
   int8_t ref_deltas[8], mode_deltas[2];
