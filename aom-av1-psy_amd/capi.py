@@ -156,6 +156,16 @@ scaled_block_dtype = np.dtype([(n, "<i4") for n in ("src_x", "src_y", "subpel_x_
 txfm_yrd_block_dtype = np.dtype([("bx", "<i2"), ("by", "<i2"), ("tx_size_rate", "<i4"), ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"),
                                  ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])   # aomhip_txfm_yrd_block
 txfm_yrd_stats_dtype = np.dtype([("rd", "<i8"), ("dist", "<i8"), ("sse", "<i8"), ("rate", "<i4"), ("skip_txfm", "<i4")])   # aomhip_txfm_yrd_stats
+# aomhip_tx_search_block (32 bytes), aomhip_tx_type_entry (32), aomhip_tx_search_info (16), aomhip_tx_search_result (40): aomhip_search_tx_type_batch
+TX_SEARCH_TRACE_BYTES = 17
+tx_search_block_dtype = np.dtype([("x", "<i4"), ("y", "<i4"), ("ref_best_rd", "<i8"), ("rdmult", "<i4"), ("out_offset", "<u4"), ("allowed_tx_mask", "<u2"),
+                                  ("visible_cols", "u1"), ("visible_rows", "u1"), ("txk_allowed_single", "u1"), ("txb_skip_ctx", "u1"), ("dc_sign_ctx", "u1"),
+                                  ("reserved", "u1")])
+tx_type_entry_dtype = np.dtype([("dist", "<i8"), ("sse", "<i8"), ("px_dist", "<i8"), ("rate", "<i4"), ("eob", "<u2"), ("txb_entropy_ctx", "u1"), ("valid", "u1")])
+tx_search_info_dtype = np.dtype([("block_sse", "<i8"), ("block_mse_q8", "<u4"), ("use_transform_domain_distortion", "u1"),
+                                 ("calc_pixel_domain_distortion_final", "u1"), ("reserved", "u1", (2,))])
+tx_search_result_dtype = np.dtype([("best_rd", "<i8"), ("dist", "<i8"), ("sse", "<i8"), ("rate", "<i4"), ("best_eob", "<u2"), ("best_tx_type", "u1"),
+                                   ("txb_entropy_ctx", "u1"), ("skip_txfm", "u1"), ("reserved", "u1", (7,))])
 warp_model_dtype = np.dtype([("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2")])
 warp_refine_block_dtype = np.dtype([(n_, "<i2") for n_ in ("bx", "by", "mv_row", "mv_col", "ref_row", "ref_col", "row_min", "row_max", "col_min", "col_max")] +
                                    [("total_samples", "<i4"), ("num_proj_ref", "<i4"), ("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)),
@@ -163,6 +173,26 @@ warp_refine_block_dtype = np.dtype([(n_, "<i2") for n_ in ("bx", "by", "mv_row",
 warp_refine_result_dtype = np.dtype([("mv_row", "<i2"), ("mv_col", "<i2"), ("num_proj_ref", "<i4"), ("bestmse", "<u4"), ("model", warp_model_dtype)])
 warp_block_dtype = np.dtype([("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("p_col", "<i4"), ("p_row", "<i4"),
                              ("p_width", "<i4"), ("p_height", "<i4")])   # aomhip_warp_block (48 bytes)
+
+
+class TxSearchParams(C.Structure):
+    """aomhip_tx_search_params (include/aomhip.h)."""
+    _fields_ = [("tx_type_costs", C.c_int32 * 16), ("use_transform_domain_distortion", C.c_int32), ("tx_domain_dist_threshold", C.c_uint32),
+                ("low_txfm_rd", C.c_int32), ("adaptive_txb_search_level", C.c_int32), ("skip_tx_search", C.c_int32), ("tx_mask_limit", C.c_uint32),
+                ("predict_dc_level", C.c_int32), ("enable_trellis", C.c_int32), ("use_qmatrix", C.c_int32), ("quant_b_adapt", C.c_int32),
+                ("lossless", C.c_int32), ("is_intra", C.c_int32)]
+
+    @classmethod
+    def make(cls, tx_type_costs=None, use_transform_domain_distortion=0, tx_domain_dist_threshold=0, low_txfm_rd=0, adaptive_txb_search_level=0,
+             skip_tx_search=0, tx_mask_limit=0xFFFF, **out_of_scope):
+        p = cls()
+        for i, v in enumerate(tx_type_costs if tx_type_costs is not None else [0] * 16):
+            p.tx_type_costs[i] = int(v)
+        p.use_transform_domain_distortion, p.tx_domain_dist_threshold, p.low_txfm_rd = use_transform_domain_distortion, tx_domain_dist_threshold, low_txfm_rd
+        p.adaptive_txb_search_level, p.skip_tx_search, p.tx_mask_limit = adaptive_txb_search_level, skip_tx_search, tx_mask_limit
+        for k, v in out_of_scope.items():
+            setattr(p, k, v)
+        return p
 
 
 class CdefSearchIn(C.Structure):
@@ -361,6 +391,7 @@ _protos = {
     "aomhip_lpf_level_sse_table": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
     "aomhip_lpf_pick_level": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "aomhip_pick_filter_level_frame": (C.c_int, [_vp, _vp, _vp]),
+    "aomhip_search_tx_type_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "aomhip_compute_stats_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_plane_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp]),
     "aomhip_build_inter_pred_ex_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i]),
@@ -703,6 +734,12 @@ class Context:
                                                    int(is_hbd), d_qcoeff, d_dqcoeff, d_eob), "aomhip_quantize_b_adaptive_batch")
 
     # ---- variance
+    def search_tx_type_batch(self, src, pred, frame, tx_size, qparams, d_costs, params, d_blocks, n_blocks, d_result, d_txk_map=None, d_qcoeff=None,
+                             d_dqcoeff=None, d_table=None, d_info=None, d_trace=None):
+        """aomhip_search_tx_type_batch: search_tx_type for n_blocks transform blocks of one TX_SIZE (tx_search_block_dtype records)."""
+        check(lib.aomhip_search_tx_type_batch(self.h, C.byref(src), C.byref(pred), frame, tx_size, C.byref(qparams), d_costs, C.byref(params), d_blocks, d_txk_map,
+                                              n_blocks, d_result, d_qcoeff, d_dqcoeff, d_table, d_info, d_trace), "aomhip_search_tx_type_batch")
+
     def estimate_txfm_yrd_batch(self, src, pred, frame, bw, bh, qparams, d_costs, tx_type_rate, rdmult, lossless, d_blocks, n_blocks, d_stats):
         check(lib.aomhip_estimate_txfm_yrd_batch(self.h, C.byref(src), C.byref(pred), frame, bw, bh, C.byref(qparams), d_costs, tx_type_rate, rdmult, lossless,
                                                  d_blocks, n_blocks, d_stats), "aomhip_estimate_txfm_yrd_batch")

@@ -65,6 +65,7 @@ void *work(aomhip_ctx *ctx, size_t bytes);
 // enqueue the check of a per-block transform list (tx_type valid for tx_size; `wht_ok`: AOMHIP_TX_WHT allowed) on the context's stream
 int validate_txb_list(aomhip_ctx *ctx, const aomhip_txb *d_blocks, int n_blocks, int tx_size, bool wht_ok, bool any_type_0_15);
 constexpr int kStatusBadTxType = 1;
+constexpr int kStatusBadTxMask = 2;   // an aomhip_tx_search_block whose mask holds no transform type of the size, or that lies outside the planes
 bool tx_type_ok(int tx_size, int tx_type);  // (size, type) pairs av1_get_fwd_txfm_cfg serves, + AOMHIP_TX_WHT for TX_4X4
 
 #define AOMHIP_TRY(expr)                                                                       \

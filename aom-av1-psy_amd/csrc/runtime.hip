@@ -254,8 +254,9 @@ int aomhip_ctx_sync(aomhip_ctx *ctx) {
   const int st = *ctx->h_status;
   if (st) {
     AOMHIP_TRY(hipMemset(ctx->d_status, 0, sizeof(int)));
-    set_error("a batched call since the last synchronisation was given work-list entries it cannot process (device status 0x%x:%s); "
-              "its outputs are undefined", st, (st & kStatusBadTxType) ? " an aomhip_txb tx_type that does not exist for the transform size" : "");
+    set_error("a batched call since the last synchronisation was given work-list entries it cannot process (device status 0x%x:%s%s); "
+              "its outputs are undefined", st, (st & kStatusBadTxType) ? " an aomhip_txb tx_type that does not exist for the transform size" : "",
+              (st & kStatusBadTxMask) ? " an aomhip_tx_search_block without an allowed transform type of the size, or outside the planes" : "");
     return AOMHIP_ERR_INVALID;
   }
   return AOMHIP_OK;

@@ -2,43 +2,10 @@
 // context a coded block leaves behind.
 #include "common.h"
 #include "quant_device.h"
+#include "txb_cost_device.h"
 #include "txb_cost_table.inc"
 
 namespace aomhip {
-
-// What the two kernels below share of the level map's contexts (av1/common/txb_common.h:150-224).  L(row, col): the level map's entry at that
-// position, 0 past the block's edge (the two kernels keep their levels in different places).
-// get_nz_mag's five causal neighbours of a tx_class: `mag` sums them clipped at 3; `br` sums the nearest three unclipped (get_br_ctx's).
-struct NzMag { int mag, br; };
-template <typename Level> __device__ __forceinline__ NzMag nz_mag(int tx_class, int row, int col, Level &&L) {
-  const int l10 = L(row + 1, col), l01 = L(row, col + 1);
-  NzMag m = { min(l10, 3) + min(l01, 3), l10 + l01 };
-  if (tx_class == 0) {
-    const int l11 = L(row + 1, col + 1);
-    m.mag += min(l11, 3) + min(L(row, col + 2), 3) + min(L(row + 2, col), 3);
-    m.br += l11;
-  } else if (tx_class == 2) {
-    const int l20 = L(row + 2, col);
-    m.mag += min(l20, 3) + min(L(row + 3, col), 3) + min(L(row + 4, col), 3);
-    m.br += l20;
-  } else {
-    const int l02 = L(row, col + 2);
-    m.mag += min(l02, 3) + min(L(row, col + 3), 3) + min(L(row, col + 4), 3);
-    m.br += l02;
-  }
-  return m;
-}
-// get_nz_map_ctx_from_stats for coefficient `pos` = (row, col); the 2-D position offsets by Nz_Map's rule (av1_nz_map_ctx_offset; `rel` =
-// sign(tx_w - tx_h) of the transform's own size: TX_64X32 / TX_32X64 code 32 x 32 coefficients with the rectangular offsets)
-__device__ __forceinline__ int nz_map_ctx(int mag, int tx_class, int pos, int row, int col, int rel) {
-  if ((tx_class | pos) == 0) return 0;
-  const int ctx = min((mag + 1) >> 1, 4);
-  if (tx_class == 0) return ctx + ((rel < 0 && row < 2) ? 11 : ((rel > 0 && col < 2) ? 16 : (row + col < 2 ? 1 : (row + col < 4 ? 6 : 21))));
-  const int k = tx_class == 1 ? col : row;
-  return ctx + 26 + (k == 0 ? 0 : (k == 1 ? 5 : 10));   // SIG_COEF_CONTEXTS_2D + nz_map_ctx_offset_1d
-}
-// the context of the last coefficient, scan index i of NC (get_lower_levels_ctx_eob)
-template <int NC> __device__ __forceinline__ int eob_coeff_ctx(int i) { return i == 0 ? 0 : (i <= NC / 8 ? 1 : (i <= NC / 4 ? 2 : 3)); }
 
 // av1_get_nz_map_contexts_c (av1/encoder/encodetxb.c:222-267): the context of every coefficient before the end of block, from the magnitudes of its
 // causal neighbours in the padded level map (av1_txb_init_levels' output: aomhip_txb_init_levels_batch) -- get_nz_mag / get_nz_map_ctx_from_stats
@@ -80,23 +47,17 @@ __global__ __launch_bounds__(256) void cost_coeffs_txb_kernel(const int32_t *__r
                                                               int uniform_type, int rel, const uint16_t *__restrict__ eobs, const uint8_t *__restrict__ txb_ctx,
                                                               const int32_t *__restrict__ costs, int32_t *__restrict__ out) {
   constexpr int NC = KW * KH, BHL = KH == 4 ? 2 : (KH == 8 ? 3 : (KH == 16 ? 4 : 5));
-  constexpr int kSkip = 0, kBaseEob = 26, kBase = 38, kEobExtra = 374, kDcSign = 392, kLps = 398, kEob = 944;
   WaveBlock wb;
   if (!wave_block<NC>(blocks, n_blocks, uniform_type, wb)) return;
   const int lane = wb.lane, bi = wb.bi, scan_class = scan_class_of(wb.tx_type), tx_class = tx_class_of(wb.tx_type);
   const int64_t off = wb.off;
   const int eob = eobs[bi], skip_ctx = txb_ctx[2 * bi], dc_ctx = txb_ctx[2 * bi + 1];
   if (eob == 0) {
-    if (lane == 0) out[bi] = costs[kSkip + skip_ctx * 2 + 1];
+    if (lane == 0) out[bi] = costs[kTxbSkip + skip_ctx * 2 + 1];
     return;
   }
   const int32_t *q = qcoeff + off;
   auto L = [&](int r, int c) { return (r < KH && c < KW) ? min(abs(q[c * KH + r]), 127) : 0; };   // av1_txb_init_levels' entry (row r of column c)
-  auto br_cost = [&](int level, int ctx) {   // get_br_cost + get_golomb_cost (txb_rdopt_utils.h:85-97)
-    int c = costs[kLps + ctx * 26 + min(level - 3, 12)];
-    if (level >= 15) c += (2 * (32 - __builtin_clz(level - 14)) - 1) * 512;
-    return c;
-  };
   int acc = 0;
   for (int pos = lane; pos < NC; pos += 64) {
     const int col = pos >> BHL, row = pos & (KH - 1);
@@ -107,42 +68,11 @@ __global__ __launch_bounds__(256) void cost_coeffs_txb_kernel(const int32_t *__r
       acc += i == eob - 1 ? (level - 1) * 2048 : kTxbCostLut[min(level, 14)];
       continue;
     }
-    if (i == eob - 1) {
-      acc += costs[kBaseEob + eob_coeff_ctx<NC>(i) * 3 + min(level, 3) - 1];
-      if (v) {
-        if (level > 2) {
-          const bool near = (tx_class == 0 && row < 2 && col < 2) || (tx_class == 1 && col == 0) || (tx_class == 2 && row == 0);
-          acc += br_cost(level, pos == 0 ? 0 : (near ? 7 : 14));   // get_br_ctx_eob
-        }
-        acc += i ? 512 : costs[kDcSign + dc_ctx * 2 + (v < 0)];
-      }
-      continue;
-    }
-    // the nz-map context (get_nz_mag / get_nz_map_ctx_from_stats, clipped at 3) and, for levels above NUM_BASE_LEVELS, get_br_ctx (unclipped)
-    const NzMag m = nz_mag(tx_class, row, col, L);
-    acc += costs[kBase + nz_map_ctx(m.mag, tx_class, pos, row, col, rel) * 8 + min(level, 3)];
-    if (v) {
-      acc += i ? 512 : costs[kDcSign + dc_ctx * 2 + (v < 0)];
-      if (level > 2) {
-        int b = min((m.br + 1) >> 1, 6);
-        if (pos != 0) {
-          const bool near = (tx_class == 0 && row < 2 && col < 2) || (tx_class == 1 && col == 0) || (tx_class == 2 && row == 0);
-          b += near ? 7 : 14;
-        }
-        acc += br_cost(level, b);
-      }
-    }
+#include "txb_coeff_cost_term.inc"
   }
   for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m, 64);
   if (lane == 0) {
-    // get_eob_cost (txb_rdopt_utils.h:66-83) with av1_get_eob_pos_token: group t = the last one whose start (1, 2, 3, 5, 9, 17, ..) is <= eob
-    const int t = eob < 3 ? eob : 33 - __builtin_clz(eob - 1);
-    const int bits = t < 3 ? 0 : t - 2;   // av1_eob_offset_bits
-    int c = costs[kSkip + skip_ctx * 2] + costs[kEob + (tx_class == 0 ? 0 : 11) + t - 1];
-    if (bits > 0) {
-      const int extra = eob - ((1 << (t - 2)) + 1);   // av1_eob_group_start[t] for t >= 3
-      c += costs[kEobExtra + (t - 3) * 2 + ((extra >> (bits - 1)) & 1)] + (bits - 1) * 512;
-    }
+    const int c = txb_block_cost(costs, eob, skip_ctx, tx_class);
     out[bi] = acc + c + (LAPLACIAN ? (512 + 739) * (eob - 1) : 0);   // const_term + loge_par
   }
 }

@@ -1490,6 +1490,86 @@ int aomhip_estimate_txfm_yrd_batch(aomhip_ctx *ctx, const aomhip_planes *src, co
                                    const aomhip_quant_params *qparams, const int32_t *d_costs, int tx_type_rate, int rdmult, int lossless,
                                    const aomhip_txfm_yrd_block *d_blocks, int n_blocks, aomhip_txfm_yrd_stats *d_stats);
 
+/* search_tx_type (av1/encoder/tx_search.c:2019-2335) for a batch of transform blocks of ONE TX_SIZE and one plane type of INTER blocks: the loop
+ * over the allowed transform types with its `continue` and `break` statements, the winner, its RD_STATS and the tail (skip_txfm, the final
+ * pixel-domain distortion of :2324-2328).  Three stream-ordered steps:
+ *   table   one kernel stages each block's source and predictor tile once and evaluates every allowed type from LDS: av1_xform + av1_quant
+ *           (AV1_XFORM_QUANT_B, USE_B_QUANT_NO_TRELLIS), cost_coeffs -> av1_cost_coeffs_txb + get_tx_type_cost, the entropy context,
+ *           dist_block_tx_domain, and -- where the branch structure of :2185-2236 or the final recomputation needs it -- dist_block_px_domain
+ *           (inverse transform, clipped add onto the predictor, SSE over the visible part with the high-bit-depth rounding of the variance
+ *           functions).  One aomhip_tx_type_entry per (block, type): what this_rd_stats would hold if the loop reached that type.
+ *   walk    one thread per block replays :2145-2309 on the table (txk_map order under the mask, the rate-only `continue`, strict `rd < best_rd`,
+ *           the adaptive_txb_search_level and skip_tx_search breaks) and the tail.
+ *   coeffs  only when d_qcoeff or d_dqcoeff is given: aomhip_subtract_xform_quant_ex_batch's kernel once, each block with its winning type.
+ * No synchronisation and no device-to-host copy once the context's work memory is large enough: graph-capturable after one warm-up call; the
+ * launch sequence depends on tx_size, the planes' bit depth and which outputs are requested only.
+ * OUT OF SCOPE, left with the caller (a parameter that could express one of them must be 0, else AOMHIP_ERR_INVALID): get_tx_mask and its pruning
+ * (ML model included: its outputs are this call's inputs), trellis optimisation (av1_optimize_b: skip_trellis == 1, so perform_block_coeff_opt and
+ * skip_trellis_opt_based_on_satd have no effect), predict_dc_level >= 1, quantisation matrices and quant_b_adapt, lossless, intra blocks (recon_intra
+ * is a no-op for inter blocks, :879), the intra-frame hash, and writes to tx_type_map (update_txk_array stays on the host, driven by best_tx_type). */
+typedef struct {
+  int32_t tx_type_costs[16];               /* get_tx_type_cost's addend per TX_TYPE for this size and the block class's transform set (all 0 for the
+                                              64-point sizes); added only when eob > 0, as in the reference */
+  int32_t use_transform_domain_distortion; /* txfm_params->use_transform_domain_distortion (0, 1, 2) as the loop sees it: 0 under AOM_CONTENT_PSY */
+  uint32_t tx_domain_dist_threshold;       /* txfm_params->tx_domain_dist_threshold */
+  int32_t low_txfm_rd;                     /* x->rd_model == LOW_TXFM_RD */
+  int32_t adaptive_txb_search_level;       /* sf.tx_sf.adaptive_txb_search_level (0 .. 62) */
+  int32_t skip_tx_search;                  /* sf.tx_sf.tx_type_search.skip_tx_search */
+  uint32_t tx_mask_limit;                  /* every block's allowed_tx_mask is ANDed with this one; the call is refused when it holds no type that
+                                              exists for tx_size.  (A block whose OWN mask holds none sets the context's device status, reported by
+                                              aomhip_ctx_sync like a bad aomhip_txb, and gets best_tx_type 255.) */
+  int32_t predict_dc_level, enable_trellis, use_qmatrix, quant_b_adapt, lossless, is_intra;   /* out of scope: must be 0 */
+} aomhip_tx_search_params; /* 112 bytes */
+typedef struct {
+  int32_t x, y;                  /* the transform block's top-left sample in the plane, pixels relative to the visible origin (the planes' borders must cover
+                                    the whole block) */
+  int64_t ref_best_rd;
+  int32_t rdmult;
+  uint32_t out_offset;           /* first coefficient of this block in d_qcoeff / d_dqcoeff */
+  uint16_t allowed_tx_mask;      /* get_tx_mask's return value */
+  uint8_t visible_cols, visible_rows;   /* get_txb_dimensions: 1 .. the transform's width / height; pixel_diff_dist and pixel_dist_visible_only read this part only */
+  uint8_t txk_allowed_single;    /* txk_allowed < TX_TYPES (tested apart from the mask at :2128-2130) */
+  uint8_t txb_skip_ctx, dc_sign_ctx;    /* TXB_CTX */
+  uint8_t reserved;
+} aomhip_tx_search_block; /* 32 bytes */
+typedef struct {
+  int64_t dist, sse;             /* this_rd_stats.dist / .sse after :2185-2236 */
+  int64_t px_dist;               /* dist_block_px_domain of this type where the kernel computed it (the branch needed it, or the final recomputation is on), else -1 */
+  int32_t rate;                  /* rate_cost */
+  uint16_t eob;
+  uint8_t txb_entropy_ctx;
+  uint8_t valid;                 /* 0: the type is outside the block's mask or does not exist for the size (the other fields are 0) */
+} aomhip_tx_type_entry; /* 32 bytes */
+typedef struct {
+  int64_t block_sse;             /* as the loop uses it: pixel_diff_dist, rounded for the bit depth, times 16 */
+  uint32_t block_mse_q8;         /* rounded for the bit depth */
+  uint8_t use_transform_domain_distortion, calc_pixel_domain_distortion_final;   /* the two flags after :2112-2130 */
+  uint8_t reserved[2];
+} aomhip_tx_search_info; /* 16 bytes */
+typedef struct {
+  int64_t best_rd;
+  int64_t dist, sse;             /* best_rd_stats, the final pixel-domain recomputation included */
+  int32_t rate;
+  uint16_t best_eob;
+  uint8_t best_tx_type;          /* 255: the block's mask held no type that exists for the size */
+  uint8_t txb_entropy_ctx;
+  uint8_t skip_txfm;
+  uint8_t reserved[7];
+} aomhip_tx_search_result; /* 40 bytes */
+#define AOMHIP_TX_SEARCH_TRACE_BYTES 17
+/*   src / pred / frame   as aomhip_subtract_xform_quant_ex_batch takes them (same visible geometry and bit depth: 8, 10 or 12)
+ *   d_costs              the 966 ints of aomhip_cost_coeffs_txb_batch
+ *   d_txk_map            [n_blocks][16] TX_TYPEs in visiting order, 255 = TX_TYPE_INVALID; NULL: the identity order for every block
+ *   d_result             [n_blocks]
+ *   d_qcoeff / d_dqcoeff both NULL, or both given: the winner's coefficients at out_offset (as aomhip_subtract_xform_quant_ex_batch writes them for that type)
+ *   d_table / d_info     NULL, or [n_blocks][16] entries indexed by TX_TYPE / [n_blocks] scalars
+ *   d_trace              NULL, or AOMHIP_TX_SEARCH_TRACE_BYTES per block: [0] = how many types the reference's loop would have visited (got past the
+ *                        mask test), [1 ..] those types in order */
+int aomhip_search_tx_type_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *pred, int frame, int tx_size,
+                                const aomhip_quant_params *qparams, const int32_t *d_costs, const aomhip_tx_search_params *params,
+                                const aomhip_tx_search_block *d_blocks, const uint8_t *d_txk_map, int n_blocks, aomhip_tx_search_result *d_result,
+                                int32_t *d_qcoeff, int32_t *d_dqcoeff, aomhip_tx_type_entry *d_table, aomhip_tx_search_info *d_info, uint8_t *d_trace);
+
 /* aomhip_single_motion_search_batch with the RD form of the second-MV decision (sf.mv_sf.use_accurate_subpel_search, disable_second_mv == 0; :378-425): after the sub-pel
  * search from best_mv and -- where try_second holds and the start is inside the sub-pel limits -- from second_best_mv, each candidate's
  * predictor is built into rd->pred (frame `frame` of a ring with the source's geometry; av1_enc_build_inter_predictor, luma, filters
