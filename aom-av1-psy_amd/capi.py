@@ -166,6 +166,13 @@ tx_search_info_dtype = np.dtype([("block_sse", "<i8"), ("block_mse_q8", "<u4"), 
                                  ("calc_pixel_domain_distortion_final", "u1"), ("reserved", "u1", (2,))])
 tx_search_result_dtype = np.dtype([("best_rd", "<i8"), ("dist", "<i8"), ("sse", "<i8"), ("rate", "<i4"), ("best_eob", "<u2"), ("best_tx_type", "u1"),
                                    ("txb_entropy_ctx", "u1"), ("skip_txfm", "u1"), ("reserved", "u1", (7,))])
+# aomhip_uniform_tx_block (112 bytes), aomhip_uniform_tx_stats (56), aomhip_uniform_tx_txb (4): the uniform transform-size search
+UNIFORM_TX_MAX_TXB = 64
+uniform_tx_block_dtype = np.dtype([("x", "<i4"), ("y", "<i4"), ("rdmult", "<i4"), ("source_variance", "<u4"), ("ref_best_rd", "<i8"), ("tx_size_rate", "<i4", (3,)),
+                                   ("no_skip_txfm_rate", "<i4"), ("skip_txfm_rate", "<i4"), ("coeff_offset", "<u4"), ("above_ctx", "u1", (32,)), ("left_ctx", "u1", (32,))])
+uniform_tx_stats_dtype = np.dtype([("rd", "<i8"), ("dist", "<i8"), ("sse", "<i8"), ("rate", "<i4"), ("skip_txfm", "u1"), ("tx_size", "u1"), ("n_txb", "<u2"),
+                                   ("depth_rd", "<i8", (3,))])
+uniform_tx_txb_dtype = np.dtype([("tx_type", "u1"), ("blk_skip", "u1"), ("txb_entropy_ctx", "u1"), ("reserved", "u1")])
 warp_model_dtype = np.dtype([("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2")])
 warp_refine_block_dtype = np.dtype([(n_, "<i2") for n_ in ("bx", "by", "mv_row", "mv_col", "ref_row", "ref_col", "row_min", "row_max", "col_min", "col_max")] +
                                    [("total_samples", "<i4"), ("num_proj_ref", "<i4"), ("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)),
@@ -193,6 +200,37 @@ class TxSearchParams(C.Structure):
         for k, v in out_of_scope.items():
             setattr(p, k, v)
         return p
+
+
+class UniformTxPlan(C.Structure):
+    """aomhip_uniform_tx_plan (include/aomhip.h)."""
+    _fields_ = [("n", C.c_int32), ("init_depth", C.c_int32), ("use_largest", C.c_int32), ("depth", C.c_int32 * 3), ("tx_size", C.c_int32 * 3),
+                ("reserved", C.c_int32)]
+
+    def entries(self):
+        return [(int(self.depth[k]), int(self.tx_size[k])) for k in range(self.n)]
+
+
+class UniformTxDepth(C.Structure):
+    """aomhip_uniform_tx_depth (include/aomhip.h)."""
+    _fields_ = [("params", C.POINTER(TxSearchParams)), ("d_costs", C.c_void_p), ("d_txb_masks", C.c_void_p), ("d_txk_single", C.c_void_p)]
+
+
+def uniform_tx_depths(entries):
+    """[(TxSearchParams, d_costs, d_txb_masks or None, d_txk_single or None), ..] -> an aomhip_uniform_tx_depth array (the params objects must outlive it)"""
+    arr = (UniformTxDepth * max(len(entries), 1))()
+    for k, (prm, d_costs, d_masks, d_single) in enumerate(entries):
+        arr[k].params, arr[k].d_costs, arr[k].d_txb_masks, arr[k].d_txk_single = C.pointer(prm), d_costs, d_masks, d_single
+    return arr
+
+
+def uniform_tx_depth_plan(bsize, tx_select, mode_tx_size, init_depth, enable_tx64, enable_rect_tx, use_largest):
+    """aomhip_uniform_tx_depth_plan (host only) -> UniformTxPlan; ValueError where the helper refuses its arguments."""
+    plan = UniformTxPlan()
+    if lib.aomhip_uniform_tx_depth_plan(bsize, tx_select, mode_tx_size, init_depth, enable_tx64, enable_rect_tx, use_largest, C.byref(plan)) != OK:
+        raise ValueError("aomhip_uniform_tx_depth_plan(%d, %d, %d, %d, %d, %d, %d): invalid argument"
+                         % (bsize, tx_select, mode_tx_size, init_depth, enable_tx64, enable_rect_tx, use_largest))
+    return plan
 
 
 class CdefSearchIn(C.Structure):
@@ -392,6 +430,11 @@ _protos = {
     "aomhip_lpf_pick_level": (C.c_int, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "aomhip_pick_filter_level_frame": (C.c_int, [_vp, _vp, _vp]),
     "aomhip_search_tx_type_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "aomhip_uniform_tx_depth_plan": (C.c_int, [_i, _i, _i, _i, _i, _i, _i, _vp]),
+    "aomhip_uniform_tx_size_legal": (C.c_int, [_i, _i]),
+    "aomhip_uniform_tx_plan_legal": (C.c_int, [_i, _vp]),
+    "aomhip_uniform_txfm_yrd_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "aomhip_pick_uniform_tx_size_type_yrd_batch": (C.c_int, [_vp, _PP, _PP, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "aomhip_compute_stats_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "aomhip_plane_sse": (C.c_int, [_vp, _PP, _i, _PP, _i, _vp]),
     "aomhip_build_inter_pred_ex_batch": (C.c_int, [_vp, _PP, _i, _PP, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i]),
@@ -739,6 +782,17 @@ class Context:
         """aomhip_search_tx_type_batch: search_tx_type for n_blocks transform blocks of one TX_SIZE (tx_search_block_dtype records)."""
         check(lib.aomhip_search_tx_type_batch(self.h, C.byref(src), C.byref(pred), frame, tx_size, C.byref(qparams), d_costs, C.byref(params), d_blocks, d_txk_map,
                                               n_blocks, d_result, d_qcoeff, d_dqcoeff, d_table, d_info, d_trace), "aomhip_search_tx_type_batch")
+
+    def uniform_txfm_yrd_batch(self, src, pred, frame, bsize, tx_size, qparams, depth, d_blocks, n_blocks, d_stats, d_txb):
+        """aomhip_uniform_txfm_yrd_batch: av1_uniform_txfm_yrd at one TX_SIZE for n_blocks prediction blocks (uniform_tx_block_dtype records); depth: a
+        one-entry uniform_tx_depths array."""
+        check(lib.aomhip_uniform_txfm_yrd_batch(self.h, C.byref(src), C.byref(pred), frame, bsize, tx_size, C.byref(qparams), depth, d_blocks, n_blocks, d_stats, d_txb),
+              "aomhip_uniform_txfm_yrd_batch")
+
+    def pick_uniform_tx_size_type_yrd_batch(self, src, pred, frame, bsize, plan, qparams, depths, d_blocks, n_blocks, d_stats, d_txb, d_qcoeff=None, d_dqcoeff=None):
+        """aomhip_pick_uniform_tx_size_type_yrd_batch: choose_tx_size_type_from_rd / choose_largest_tx_size over a plan of uniform_tx_depth_plan."""
+        check(lib.aomhip_pick_uniform_tx_size_type_yrd_batch(self.h, C.byref(src), C.byref(pred), frame, bsize, C.byref(plan), C.byref(qparams), depths, d_blocks,
+                                                             n_blocks, d_stats, d_txb, d_qcoeff, d_dqcoeff), "aomhip_pick_uniform_tx_size_type_yrd_batch")
 
     def estimate_txfm_yrd_batch(self, src, pred, frame, bw, bh, qparams, d_costs, tx_type_rate, rdmult, lossless, d_blocks, n_blocks, d_stats):
         check(lib.aomhip_estimate_txfm_yrd_batch(self.h, C.byref(src), C.byref(pred), frame, bw, bh, C.byref(qparams), d_costs, tx_type_rate, rdmult, lossless,

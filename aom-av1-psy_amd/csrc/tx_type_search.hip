@@ -20,6 +20,7 @@
 #include "common.h"
 #include "quant_device.h"
 #include "search_chain.h"
+#include "tx_type_walk.h"
 #include "txb_cost_device.h"
 #include "txfm_device.h"
 
@@ -43,7 +44,6 @@ template <int LPB> __device__ __forceinline__ int group_sum(int v) {
   for (int m = 1; m < LPB; m <<= 1) v += __shfl_xor(v, m, 64);
   return v;
 }
-__device__ __forceinline__ int64_t rdcost_of(int rdmult, int64_t rate, int64_t dist) { return ((rate * rdmult + 256) >> 9) + dist * 128; }   // RDCOST, rd.h:31-33
 
 template <typename T, int W, int H, int BD>
 __global__ __launch_bounds__((tts_threads<W, H>())) void tx_type_table_kernel(const T *__restrict__ src_origin, const T *__restrict__ pred_origin,
@@ -301,42 +301,23 @@ __global__ __launch_bounds__(256) void tx_type_walk_kernel(const aomhip_tx_searc
   if (i >= n) return;
   const aomhip_tx_search_block b = blocks[i];
   const aomhip_tx_type_entry *tab = table + (int64_t)i * 16;
-  const unsigned mask = b.allowed_tx_mask & mask_limit;
-  int64_t best_rd = INT64_MAX;
-  aomhip_tx_search_result o = {};
-  o.rate = INT32_MAX; o.dist = INT64_MAX; o.sse = INT64_MAX;   // av1_invalid_rd_stats
-  o.best_tx_type = 255;
-  int best_eob = 0, visited = 0;
-  for (int idx = 0; idx < 16; ++idx) {
-    const int t = txk_map ? txk_map[(int64_t)i * 16 + idx] : idx;
-    if (t > 15 || !((mask >> t) & 1u)) continue;
-    const aomhip_tx_type_entry e = tab[t];
-    if (!e.valid) continue;   // (a type that does not exist for the size: get_tx_mask never allows one)
-    if (trace) trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES + 1 + visited] = (uint8_t)t;
-    ++visited;
-    if (rdcost_of(b.rdmult, e.rate, 0) > best_rd) continue;
-    const int64_t rd = rdcost_of(b.rdmult, e.rate, e.dist);
-    if (rd < best_rd) {
-      best_rd = rd;
-      o.rate = e.rate; o.dist = e.dist; o.sse = e.sse;
-      o.best_tx_type = (uint8_t)t;
-      o.txb_entropy_ctx = e.txb_entropy_ctx;
-      best_eob = e.eob;
-    }
-    if (adaptive_level && (best_rd - (best_rd >> adaptive_level)) > b.ref_best_rd) break;
-    if (skip_tx_search && !best_eob) break;
-  }
+  const aomhip_tx_search_info inf = info[i];
+  const TxTypeWinner w = tx_type_loop(
+      b.allowed_tx_mask & mask_limit, b.rdmult, b.ref_best_rd, adaptive_level, skip_tx_search, inf.calc_pixel_domain_distortion_final != 0, inf.block_sse,
+      [&](int idx) { return txk_map ? (int)txk_map[(int64_t)i * 16 + idx] : idx; }, [&](int t) { return tx_type_head(tab[t]); },
+      [&](int t) { return TxTypeTail{ tab[t].sse, tab[t].px_dist }; },
+      [&](int k, int t) { if (trace) trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES + 1 + k] = (uint8_t)t; });
   if (trace) {
-    trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES] = (uint8_t)visited;
-    for (int k = visited; k < 16; ++k) trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES + 1 + k] = 255;
+    trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES] = (uint8_t)w.visited;
+    for (int k = w.visited; k < 16; ++k) trace[(int64_t)i * AOMHIP_TX_SEARCH_TRACE_BYTES + 1 + k] = 255;
   }
-  o.best_rd = best_rd;
-  o.best_eob = (uint16_t)best_eob;
-  o.skip_txfm = best_eob == 0;
-  if (o.best_tx_type != 255 && info[i].calc_pixel_domain_distortion_final && best_eob) {   // :2324-2328: the table holds that distortion for every type
-    o.dist = tab[o.best_tx_type].px_dist;
-    o.sse = info[i].block_sse;
-  }
+  aomhip_tx_search_result o = {};
+  o.best_rd = w.best_rd;
+  o.rate = w.rate; o.dist = w.dist; o.sse = w.sse;
+  o.best_tx_type = (uint8_t)w.best_tx_type;
+  o.txb_entropy_ctx = (uint8_t)w.txb_entropy_ctx;
+  o.best_eob = (uint16_t)w.best_eob;
+  o.skip_txfm = w.best_eob == 0;
   result[i] = o;
 }
 
@@ -375,6 +356,49 @@ int launch_table(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes 
 }
 
 }  // namespace
+
+bool tx_search_params_ok(const char *who, int tx_size, const aomhip_tx_search_params *params) {
+  if (params->predict_dc_level || params->enable_trellis || params->use_qmatrix || params->quant_b_adapt || params->lossless || params->is_intra) {
+    set_error("%s: predict_dc_level, trellis, quantisation matrices, quant_b_adapt, lossless and intra blocks stay with the caller", who);
+    return false;
+  }
+  if (params->use_transform_domain_distortion < 0 || params->use_transform_domain_distortion > 2 || params->adaptive_txb_search_level < 0 ||
+      params->adaptive_txb_search_level > 62) {
+    set_error("%s: use_transform_domain_distortion is 0, 1 or 2; adaptive_txb_search_level 0 .. 62", who);
+    return false;
+  }
+  const int w = kTxWide[tx_size], h = kTxHigh[tx_size];
+  bool any = false;
+  for (int t = 0; t < 16; ++t) any |= ((params->tx_mask_limit >> t) & 1u) && tx_type_exists(w, h, t);
+  if (!any) {
+    set_error("%s: tx_mask_limit 0x%x holds no transform type that exists for a %d x %d transform", who, params->tx_mask_limit, w, h);
+    return false;
+  }
+  return true;
+}
+
+int tx_type_table_launch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *pred, int frame, int tx_size, const aomhip_quant_params *qparams,
+                         const int32_t *d_costs, const aomhip_tx_search_params *params, const aomhip_tx_search_block *d_blocks, int n_blocks,
+                         aomhip_tx_type_entry *table, aomhip_tx_search_info *info) {
+  const int w = kTxWide[tx_size], h = kTxHigh[tx_size];
+  TtsArgs a = {};
+  a.n_blocks = n_blocks;
+  a.src_stride = src->stride; a.pred_stride = pred->stride;
+  a.use_txd = params->use_transform_domain_distortion; a.low_txfm_rd = params->low_txfm_rd != 0;
+  a.txd_threshold = params->tx_domain_dist_threshold; a.mask_limit = params->tx_mask_limit & 0xFFFFu;
+  const int border = src->border < pred->border ? src->border : pred->border;
+  a.x_min = -border; a.y_min = -border;
+  a.x_max = src->width + border - w; a.y_max = src->height + border - h;
+  for (int t = 0; t < 16; ++t) a.tx_type_costs[t] = params->tx_type_costs[t];
+  const QuantArgs qa = to_quant_args(qparams, 0);
+  const int bd = src->bit_depth;
+  return with_tx_size(tx_size, [&](auto w_, auto h_) -> int {
+    if (bd == 8) return launch_table<uint8_t, w_, h_, 8>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
+    if (bd == 10) return launch_table<uint16_t, w_, h_, 10>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
+    return launch_table<uint16_t, w_, h_, 12>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
+  });
+}
+
 }  // namespace aomhip
 
 using namespace aomhip;
@@ -393,22 +417,7 @@ extern "C" int aomhip_search_tx_type_batch(aomhip_ctx *ctx, const aomhip_planes 
     set_error("aomhip_search_tx_type_batch: bad tx_size or frame index, or source and predictor planes of different geometry or bit depth");
     return AOMHIP_ERR_INVALID;
   }
-  if (params->predict_dc_level || params->enable_trellis || params->use_qmatrix || params->quant_b_adapt || params->lossless || params->is_intra) {
-    set_error("aomhip_search_tx_type_batch: predict_dc_level, trellis, quantisation matrices, quant_b_adapt, lossless and intra blocks stay with the caller");
-    return AOMHIP_ERR_INVALID;
-  }
-  if (params->use_transform_domain_distortion < 0 || params->use_transform_domain_distortion > 2 || params->adaptive_txb_search_level < 0 ||
-      params->adaptive_txb_search_level > 62) {
-    set_error("aomhip_search_tx_type_batch: use_transform_domain_distortion is 0, 1 or 2; adaptive_txb_search_level 0 .. 62");
-    return AOMHIP_ERR_INVALID;
-  }
-  const int w = kTxWide[tx_size], h = kTxHigh[tx_size];
-  bool any = false;
-  for (int t = 0; t < 16; ++t) any |= ((params->tx_mask_limit >> t) & 1u) && tx_type_exists(w, h, t);
-  if (!any) {
-    set_error("aomhip_search_tx_type_batch: tx_mask_limit 0x%x holds no transform type that exists for a %d x %d transform", params->tx_mask_limit, w, h);
-    return AOMHIP_ERR_INVALID;
-  }
+  if (!tx_search_params_ok("aomhip_search_tx_type_batch", tx_size, params)) return AOMHIP_ERR_INVALID;
   if ((d_qcoeff != nullptr) != (d_dqcoeff != nullptr)) {
     set_error("aomhip_search_tx_type_batch: d_qcoeff and d_dqcoeff are written together: give both or neither");
     return AOMHIP_ERR_INVALID;
@@ -422,25 +431,11 @@ extern "C" int aomhip_search_tx_type_batch(aomhip_ctx *ctx, const aomhip_planes 
   aomhip_tx_type_entry *table = d_table ? d_table : m.table;
   aomhip_tx_search_info *info = d_info ? d_info : m.info;
 
-  TtsArgs a = {};
-  a.n_blocks = n_blocks;
-  a.src_stride = src->stride; a.pred_stride = pred->stride;
-  a.use_txd = params->use_transform_domain_distortion; a.low_txfm_rd = params->low_txfm_rd != 0;
-  a.txd_threshold = params->tx_domain_dist_threshold; a.mask_limit = params->tx_mask_limit & 0xFFFFu;
-  const int border = src->border < pred->border ? src->border : pred->border;
-  a.x_min = -border; a.y_min = -border;
-  a.x_max = src->width + border - w; a.y_max = src->height + border - h;
-  for (int t = 0; t < 16; ++t) a.tx_type_costs[t] = params->tx_type_costs[t];
-  const QuantArgs qa = to_quant_args(qparams, 0);
-  const int bd = src->bit_depth;
-  int rc = with_tx_size(tx_size, [&](auto w_, auto h_) -> int {
-    if (bd == 8) return launch_table<uint8_t, w_, h_, 8>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
-    if (bd == 10) return launch_table<uint16_t, w_, h_, 10>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
-    return launch_table<uint16_t, w_, h_, 12>(ctx, src, pred, frame, d_blocks, a, qa, d_costs, table, info);
-  });
+  const unsigned mask_limit = params->tx_mask_limit & 0xFFFFu;
+  int rc = tx_type_table_launch(ctx, src, pred, frame, tx_size, qparams, d_costs, params, d_blocks, n_blocks, table, info);
   if (rc != AOMHIP_OK) return rc;
   const dim3 grid((unsigned)((n_blocks + 255) / 256)), block(256);
-  hipLaunchKernelGGL(tx_type_walk_kernel, grid, block, 0, ctx->stream, d_blocks, d_txk_map, n_blocks, table, info, a.mask_limit,
+  hipLaunchKernelGGL(tx_type_walk_kernel, grid, block, 0, ctx->stream, d_blocks, d_txk_map, n_blocks, table, info, mask_limit,
                      params->adaptive_txb_search_level, (int)(params->skip_tx_search != 0), d_result, d_trace);
   AOMHIP_LAUNCH_CHECK();
   if (coef_arrays) {

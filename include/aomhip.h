@@ -1570,6 +1570,110 @@ int aomhip_search_tx_type_batch(aomhip_ctx *ctx, const aomhip_planes *src, const
                                 const aomhip_tx_search_block *d_blocks, const uint8_t *d_txk_map, int n_blocks, aomhip_tx_search_result *d_result,
                                 int32_t *d_qcoeff, int32_t *d_dqcoeff, aomhip_tx_type_entry *d_table, aomhip_tx_search_info *d_info, uint8_t *d_trace);
 
+/* The uniform transform-size search of an INTER block's luma plane (av1/encoder/tx_search.c): the three loops around search_tx_type as one
+ * device pass over a batch of prediction blocks of ONE block size.
+ *   block_rd_txfm (:2935-3014) through av1_txfm_rd_in_plane (:3692-3735)   the transform blocks of a prediction block in
+ *       av1_foreach_transformed_block_in_plane's order (encodemb.c:551-591: 64x64 units first for the 128-class sizes, raster inside a unit;
+ *       transform blocks wholly outside the frame -- max_block_wide / max_block_high -- are not visited, partially visible ones carry
+ *       get_txb_dimensions' visible extent, rdopt_utils.h:307-341), get_txb_ctx (txb_common.h:446-460, plane 0, the plane_bsize ==
+ *       txsize_to_bsize[tx_size] case included) on the RUNNING above / left entropy contexts, search_tx_type with ref_best_rd = best_rd -
+ *       current_rd (:2973-2975), av1_set_txb_context (encodemb.h:142-148: txw_unit / txh_unit entries, not clipped at the frame edge),
+ *       rd = min(RDCOST(rate, dist), RDCOST(0, sse)), skip_txfm &= !eob, av1_merge_rd_stats (rd.h:155-179), exit_early when current_rd > best_rd,
+ *       incomplete_exit only when another transform block would still have been visited (an inter block whose budget runs out on its LAST
+ *       transform block keeps valid stats, :3728), and the entry test current_rd > ref_best_rd (:3705-3708);
+ *   av1_uniform_txfm_yrd (:3140-3199)   the header rates in front and behind, the forced-skip check temp_skip_txfm_rd <= rd (:3186-3196);
+ *   choose_tx_size_type_from_rd (:2838-2931)   up to three depths: strict rd[depth] < best_rd, the low-variance break of :2913-2916 with its
+ *       rd[depth - 1] != INT64_MAX guard; choose_largest_tx_size (:2659-2754) is the one-size form WITHOUT av1_uniform_txfm_yrd's tail.
+ * Per depth three stream-ordered steps: a LIST kernel expands the block records into aomhip_tx_search_block records in visiting order with
+ * TXB_CTX (0, 0); aomhip_search_tx_type_batch's TABLE kernel runs over that list unchanged; a WALK kernel (16 lanes per prediction block, lane t on
+ * table entry t, its contexts in LDS) re-bases every entry's rate to the real contexts -- the rate depends on them through txb_skip_cost[ctx][eob == 0] and,
+ * for a non-zero DC level, dc_sign_cost[ctx][sign] only, and the sign is in the entry's entropy context --, replays search_tx_type's loop and
+ * tail, merges, updates contexts and budget, and applies the exits, the function's tail and the depth decision.  No synchronisation and no
+ * device-to-host copy once the context's work memory is large enough: graph-capturable after one warm-up call; the launch sequence depends on
+ * the block size, the plan and the planes' bit depth only.
+ * OUT OF SCOPE, left with the caller (AOMHIP_ERR_INVALID where a parameter could express it): everything aomhip_search_tx_type_batch leaves
+ * with the caller, get_tx_mask's reordering of txk_map (every transform block visits its types in TX_TYPE order), intra blocks (and the NN
+ * depth prune), lossless (choose_smallest_tx_size), the residue-hash record, predict_skip_txfm, chroma (av1_txfm_uvrd), the recursive
+ * partition search (select_tx_size_and_type). */
+#define AOMHIP_UNIFORM_TX_MAX_TXB 64   /* 128x128 at TX_16X16: the most transform blocks a legal uniform size has */
+typedef struct {
+  int32_t n;                 /* 0 .. 3 entries (0: every depth is skipped by a `continue`; the search then leaves rd_stats invalid) */
+  int32_t init_depth;        /* the loop's first depth (MAX_TX_DEPTH = 2 when !tx_select) */
+  int32_t use_largest;       /* choose_largest_tx_size: one entry, av1_txfm_rd_in_plane without av1_uniform_txfm_yrd's tail */
+  int32_t depth[3], tx_size[3];
+  int32_t reserved;
+} aomhip_uniform_tx_plan; /* 40 bytes */
+/* The ordered (depth, TX_SIZE) pairs the loop of :2880-2917 tries for BLOCK_SIZE `bsize` (av1/common/enums.h:99-124, 0 .. 21) -- host only,
+ * plain C99, no GPU call: the start_tx demotion of :2860-2863, the two `continue` conditions of :2882-2887 and the TX_4X4 break of :2910;
+ * with use_largest the single size choose_largest_tx_size arrives at (:2666-2741, the demotions computed from the transform's dimensions:
+ * capped at 32 without enable_tx64, squared to the smaller side without enable_rect_tx).
+ *   tx_select      txfm_params->tx_mode_search_type == TX_MODE_SELECT
+ *   mode_tx_size   tx_size_from_tx_mode(bsize, tx_mode_search_type) (blockd.h:1138-1147); read when !tx_select or use_largest
+ *   init_depth     get_search_init_depth's value (0 .. 2); read when tx_select && !use_largest
+ * AOMHIP_ERR_INVALID for a bsize outside 0 .. 21, an init_depth outside 0 .. 2 or a mode_tx_size that is not one of the block's uniform sizes
+ * (max_txsize_rect_lookup[bsize] and up to two steps down sub_tx_size_map). */
+int aomhip_uniform_tx_depth_plan(int bsize, int tx_select, int mode_tx_size, int init_depth, int enable_tx64, int enable_rect_tx, int use_largest,
+                                 aomhip_uniform_tx_plan *plan);
+/* 1 when tx_size is one of bsize's uniform sizes / when `plan` is what the helper produces for bsize under some setting of its other arguments
+ * (the two device calls below refuse anything else), else 0.  Host only. */
+int aomhip_uniform_tx_size_legal(int bsize, int tx_size);
+int aomhip_uniform_tx_plan_legal(int bsize, const aomhip_uniform_tx_plan *plan);
+typedef struct {
+  int32_t x, y;                 /* the prediction block's top-left luma sample relative to the visible origin: inside the frame, a multiple of 4; the block
+                                   may cross the right and bottom frame edges (the planes' borders must cover every transform block that is visited) */
+  int32_t rdmult;
+  uint32_t source_variance;     /* x->source_variance (:2913-2916); read by the pick call only */
+  int64_t ref_best_rd;
+  int32_t tx_size_rate[3];      /* per plan entry: tx_select && block_signals_txsize(bsize) ? txfm_partition_cost[txfm_partition_context(..)][0] : 0
+                                   (:3152-3158); the one-size call reads [0]; not read with use_largest */
+  int32_t no_skip_txfm_rate, skip_txfm_rate;   /* mode_costs.skip_txfm_cost[av1_get_skip_txfm_context(xd)][0], [1] */
+  uint32_t coeff_offset;        /* first coefficient of this block in d_qcoeff / d_dqcoeff (the pick call, when they are given) */
+  uint8_t above_ctx[32], left_ctx[32];         /* as aomhip_txfm_yrd_block has them */
+} aomhip_uniform_tx_block; /* 112 bytes */
+typedef struct {
+  const aomhip_tx_search_params *params;   /* this size's: type costs, distortion mode, adaptive_txb_search_level, skip_tx_search, tx_mask_limit */
+  const int32_t *d_costs;                  /* the 966 ints of aomhip_cost_coeffs_txb_batch for this size's context */
+  const uint16_t *d_txb_masks;             /* NULL (every transform block takes tx_mask_limit), or [n_blocks][AOMHIP_UNIFORM_TX_MAX_TXB] get_tx_mask
+                                              values in visiting order */
+  const uint8_t *d_txk_single;             /* NULL (0), or [n_blocks][AOMHIP_UNIFORM_TX_MAX_TXB]: txk_allowed < TX_TYPES of that transform block */
+} aomhip_uniform_tx_depth;
+typedef struct {
+  int64_t rd;                  /* av1_uniform_txfm_yrd's return value; the pick call: best_rd (use_largest, which returns none: the walk's final current_rd,
+                                  INT64_MAX when the stats are invalid) */
+  int64_t dist, sse;           /* RD_STATS as the function leaves them: INT64_MAX / INT32_MAX / skip_txfm 0 when invalid (av1_invalid_rd_stats) */
+  int32_t rate;
+  uint8_t skip_txfm;
+  uint8_t tx_size;             /* best_tx_size; 255 when rd_stats->rate == INT_MAX (mbmi->tx_size is left alone); use_largest: always the size */
+  uint16_t n_txb;              /* the transform blocks search_tx_type ran on at the size the records below belong to */
+  int64_t depth_rd[3];         /* rd[depth], INT64_MAX where the depth was not evaluated */
+} aomhip_uniform_tx_stats; /* 56 bytes */
+typedef struct {
+  uint8_t tx_type, blk_skip, txb_entropy_ctx, reserved;   /* the winner, eob == 0, what av1_set_txb_context wrote */
+} aomhip_uniform_tx_txb;
+/* av1_uniform_txfm_yrd for ONE transform size over n_blocks prediction blocks of BLOCK_SIZE bsize.  tx_size must be one of the block's uniform
+ * sizes; src / pred: the same visible geometry and bit depth (8, 10, 12).  d_stats[n_blocks]; d_txb[n_blocks][AOMHIP_UNIFORM_TX_MAX_TXB]: the
+ * first n_txb records of a block are its visited transform blocks in visiting order (written whether or not the stats end up valid).  The host
+ * loop that turns them into tx_type_map and blk_skip walks the same order -- for (r, c) over the 64x64 units, for (blk_row, blk_col) inside a
+ * unit, in steps of the transform's size in 4-sample units, skipping blk_row >= max_blocks_high or blk_col >= max_blocks_wide --, stops after
+ * n_txb records, and per record k writes blk_skip[blk_row * (bw / 4) + blk_col] = d_txb[k].blk_skip and update_txk_array's entries
+ * (blockd.h:1259-1280): tx_type_map[blk_row * stride + blk_col] = d_txb[k].tx_type and, for a 64-point size, the same at every 16x16 unit of
+ * the transform block.  A transform block whose own mask holds no type of the size sets the context's device status (aomhip_ctx_sync reports
+ * it) and invalidates its prediction block's stats. */
+int aomhip_uniform_txfm_yrd_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *pred, int frame, int bsize, int tx_size,
+                                  const aomhip_quant_params *qparams, const aomhip_uniform_tx_depth *depth, const aomhip_uniform_tx_block *d_blocks,
+                                  int n_blocks, aomhip_uniform_tx_stats *d_stats, aomhip_uniform_tx_txb *d_txb);
+/* choose_tx_size_type_from_rd -- choose_largest_tx_size when plan->use_largest -- over a plan of aomhip_uniform_tx_depth_plan (any other plan
+ * is refused); depths[k] belongs to plan entry k.  d_stats / d_txb as above, for the winning depth (rd = best_rd).
+ *   d_qcoeff / d_dqcoeff   both NULL, or both given: the winner's coefficients.  Record k of block i (k < n_txb, a valid tx_type) has its
+ *                          av1_get_max_eob(tx_size) coefficients at coeff_offset + k * av1_get_max_eob(tx_size), as
+ *                          aomhip_subtract_xform_quant_ex_batch (AOMHIP_QUANT_B) writes them for the reported type; nothing else is written (a
+ *                          block needs at most bw * bh entries).  The existing transform kernel runs once per size of the plan over that size's
+ *                          slots into work memory, and a copy kernel moves the winners' blocks out. */
+int aomhip_pick_uniform_tx_size_type_yrd_batch(aomhip_ctx *ctx, const aomhip_planes *src, const aomhip_planes *pred, int frame, int bsize,
+                                               const aomhip_uniform_tx_plan *plan, const aomhip_quant_params *qparams,
+                                               const aomhip_uniform_tx_depth *depths, const aomhip_uniform_tx_block *d_blocks, int n_blocks,
+                                               aomhip_uniform_tx_stats *d_stats, aomhip_uniform_tx_txb *d_txb, int32_t *d_qcoeff, int32_t *d_dqcoeff);
+
 /* aomhip_single_motion_search_batch with the RD form of the second-MV decision (sf.mv_sf.use_accurate_subpel_search, disable_second_mv == 0; :378-425): after the sub-pel
  * search from best_mv and -- where try_second holds and the start is inside the sub-pel limits -- from second_best_mv, each candidate's
  * predictor is built into rd->pred (frame `frame` of a ring with the source's geometry; av1_enc_build_inter_predictor, luma, filters
